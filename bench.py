@@ -8,13 +8,16 @@ src/main.py:28,1049; the kernels of libradhip_f16.so; --amp bf16 runs libradhip.
 backward (GradScaler-scaled, as src/main.py:1077-1108), FGM attack (eps 0.5 on feature_projection) + adversarial
 forward/backward + restore; then all-reduce (RCCL, N > 1), unscale + clip 3.0, AdamW, EMA, LR schedule. An utterance counts once per step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line. `roofline` is for the dominant hand-written HIP kernel of the step
-(largest total time), timed live with HIP events on its stream over the timed region;
-`cpu_baseline` times the oracle (CPU restatement, fp32) on a bounded sample on the host cores.
+Rank 0 prints ONE JSON line. A plain run does only what the headline figure needs: set-up, graph capture, W warm-up
+steps, the K timed steps, and the line (throughput, `ms_per_step`, configuration, loss). `--dump-outputs DIR` also
+writes what the last timed step left behind (see dump_outputs). `--full` adds everything else: `roofline` for the
+dominant hand-written HIP kernel of the step (largest total time) with the per-kernel and per-shape tables, timed
+with device clock stamps over a kernel-timing region of K more steps (HIP events on the launch stream with --eager),
+and `cpu_baseline`, which times the oracle (CPU restatement, fp32) on a bounded sample on the host cores.
 """
 import argparse
 import json
@@ -85,7 +88,14 @@ def parse():
     ap.add_argument("--layerdrop", type=float, default=0.0,
                     help="WavLM LayerDrop during the bench (0 = every layer runs; never less work)")
     ap.add_argument("--pool", type=int, default=64, help="synthetic utterances resident in HBM per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel timings and the roofline "
+                         "(a second graph capture and a kernel-timing region of --steps more steps) and the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (trained parameters, EMA, mean loss) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-protocol", default="bounded", choices=["bounded", "full"],
                     help="bounded: B=2 (1 warm-up + 2 timed steps) and B=8 (1 + 1), ~1 min; full: BASELINE.md §3, B=2 and B=8, "
@@ -132,6 +142,33 @@ def build(config, device, layerdrop):
     core = model.wavlm_stream._core()
     core.config.layerdrop = layerdrop
     return model
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer):
+    """What a caller of the timed path holds after its last step, as <out_dir>/<name>.npy (float32 / float64, at
+    most DUMP_MAX_BYTES in all): `params`, every trained parameter (Trainer.params order, flattened and
+    concatenated); `ema`, the EMA copy of the trainable parameters (EMA.names order); `loss`, the mean training
+    loss per utterance over the warm-up and timed steps. An array over its share of the budget is written as a
+    fixed sample (elements at sorted indices drawn from default_rng(0)), the same from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": [p.detach() for p in trainer.params]}
+    if trainer.ema is not None and trainer.ema.shadow is not None:
+        arrays["ema"] = list(trainer.ema.shadow)
+    budget = (DUMP_MAX_BYTES - 4096) // (4 * len(arrays))      # float32 elements per array; .npy headers aside
+    written = {}
+    for name, tensors in arrays.items():
+        flat = torch.cat([t.reshape(-1).float() for t in tensors]).cpu().numpy()
+        if flat.size > budget:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, budget, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), flat)
+        written[name] = int(flat.size)
+    loss = np.array([float(trainer.loss_sum.item()) / max(trainer.n_seen, 1)], dtype=np.float64)
+    np.save(os.path.join(out_dir, "loss.npy"), loss)
+    written["loss"] = 1
+    return written
 
 
 def roofline_from_rows(rows, steps, graphed=False, split=False):
@@ -404,7 +441,8 @@ def main():
         graph = GraphedMicroStep(trainer, B)
     if not args.eager:
         hb.set("capturing HIP graphs")
-        graph_timer = ops.GraphTimer(dev)
+        if args.full:
+            graph_timer = ops.GraphTimer(dev)
         if window is not None:
             # the timed region replays unstamped graphs (SincNet stream as a concurrent branch); the kernel
             # timings come from a second capture of the same window with captured clock stamps around the
@@ -416,21 +454,23 @@ def main():
                 w.capture()
                 w.reset_host()
             capture(window)
-            prev = os.environ.get("RADHIP_SINC_BRANCH")
-            os.environ["RADHIP_SINC_BRANCH"] = "0"
-            ops.CAPTURE_TIMING = graph_timer
-            try:
-                # built under the switch: the window picks its batched adversarial SincNet stream at construction
-                window_t = WindowStep(trainer, B, graphs=True)
-                capture(window_t)
-            finally:
-                ops.CAPTURE_TIMING = None
-                if prev is None:
-                    os.environ.pop("RADHIP_SINC_BRANCH")
-                else:
-                    os.environ["RADHIP_SINC_BRANCH"] = prev
+            if args.full:
+                prev = os.environ.get("RADHIP_SINC_BRANCH")
+                os.environ["RADHIP_SINC_BRANCH"] = "0"
+                ops.CAPTURE_TIMING = graph_timer
+                try:
+                    # built under the switch: the window picks its batched adversarial SincNet stream at
+                    # construction
+                    window_t = WindowStep(trainer, B, graphs=True)
+                    capture(window_t)
+                finally:
+                    ops.CAPTURE_TIMING = None
+                    if prev is None:
+                        os.environ.pop("RADHIP_SINC_BRANCH")
+                    else:
+                        os.environ["RADHIP_SINC_BRANCH"] = prev
         else:
-            ops.CAPTURE_TIMING = graph_timer    # captured clock stamps around every radhip launch in the graph
+            ops.CAPTURE_TIMING = graph_timer    # --full: clock stamps captured around every radhip launch
             graph.capture()
             ops.CAPTURE_TIMING = None
 
@@ -468,7 +508,7 @@ def main():
     torch.cuda.synchronize()
     hb.set("timed steps")
     split = window_t is not None            # kernel timings from their own region (see the capture above)
-    ops.TIMING = None if split else {}
+    ops.TIMING = {} if args.full and not split else None
     if graph_timer is not None:
         graph_timer.reset()
     stream = torch.cuda.current_stream(dev)
@@ -507,6 +547,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        hb.set("writing outputs")
+        dumped = dump_outputs(args.dump_outputs, trainer)
     if split:
         hb.set("kernel-timing steps")
         cur["window"] = window_t
@@ -517,7 +561,7 @@ def main():
         torch.cuda.synchronize()
         cur["window"] = window
     timing, ops.TIMING = ops.TIMING, None
-    rows = ops.event_rows(timing)            # eager launches (augmentation, FGM)
+    rows = ops.event_rows(timing) if args.full else {}      # eager launches (augmentation, FGM)
     shape_rows = graph_timer.rows(by_shape=True) if graph_timer is not None else {}
     if graph_timer is not None:              # launches inside the replayed graphs
         for k, r in graph_timer.rows().items():
@@ -553,21 +597,25 @@ def main():
                        "rawboost_algo": dc.get("rawboost_algo"), "codec_p": dc.get("codec_p"),
                        "wavlm_layerdrop": args.layerdrop, "lora_mode": args.lora_mode, "hip_graphs": not args.eager,
                        "window_batched_clean_passes": window is not None},
-            "roofline": roof,
             "step_mfma_frac": round(value / ws * TRAIN_FLOP_PER_UTT / 2.5e15, 4),
-            "kernels": {k: {kk: round(vv, 5) if isinstance(vv, float) else vv for kk, vv in v.items()}
-                        for k, v in rows.items()},
-            # the dominant kernel per (kernel, shape): every shape sampled in every graph (GraphTimer keys)
-            "kernel_shapes": shape_table(shape_rows, roof["kernel"] if roof else None, args.steps),
             "final_loss": round(loss, 6),
             # host time to issue the K steps (no sync inside): close to ms_per_step means the GPU waited on the host
             "host_submit_ms_per_step": round(1000 * host_submit / args.steps, 3),
+            "full": args.full,
         }
-        if ws == 1 and not args.no_cpu_baseline:
-            hb.set("cpu baseline")
-            line["cpu_baseline"] = protocol_baseline(cpu_baseline(config, cpu_threads(args), args.cpu_protocol))
-        else:
-            line["cpu_baseline"] = None
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if args.full:
+            line["roofline"] = roof
+            line["kernels"] = {k: {kk: round(vv, 5) if isinstance(vv, float) else vv for kk, vv in v.items()}
+                               for k, v in rows.items()}
+            # the dominant kernel per (kernel, shape): every shape sampled in every graph (GraphTimer keys)
+            line["kernel_shapes"] = shape_table(shape_rows, roof["kernel"] if roof else None, args.steps)
+            if ws == 1 and not args.no_cpu_baseline:
+                hb.set("cpu baseline")
+                line["cpu_baseline"] = protocol_baseline(cpu_baseline(config, cpu_threads(args), args.cpu_protocol))
+            else:
+                line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     hb.stop()
     if ws > 1:

@@ -48,13 +48,6 @@ def golden():
     return load
 
 
-REFERENCE = "/root/reference"
-
-
-def reference_present():
-    return os.path.isdir(REFERENCE)
-
-
 @pytest.fixture(autouse=True)
 def _gpu_heartbeat(request):
     """Long GPU tests (the fp32 accumulation-window test spends minutes in MIOpen's fp32 solver search

@@ -246,6 +246,24 @@ def _read_b0x(path):
     return np.array(bona), np.array(spoof), np.array(attacks)
 
 
+def gen_eval_scores(ref_root):
+    """The two baseline score files as data: every trial's score in millionths (the files print six decimals, so
+    int / 1e6 gives back exactly the float their text parses to) and its bonafide flag, in file order."""
+    out = {}
+    for name in ["B01", "B02"]:
+        path = os.path.join(ref_root, f"tDCF_python_v2/scores/{name}_LA_primary_eval.txt")
+        micro, bona = [], []
+        for ln in open(path):
+            p = ln.split()
+            m = int(round(float(p[5]) * 1e6))
+            assert m / 1e6 == float(p[5]), ln
+            micro.append(m)
+            bona.append(p[4] == "bonafide")
+        out[f"{name}_score_micro"] = np.array(micro, dtype=np.int32)
+        out[f"{name}_bonafide"] = np.array(bona, dtype=bool)
+    npz(os.path.join(HERE, "eval_scores.npz"), **out)
+
+
 def gen_eval(ref_root):
     import evaluation as EV
     import report_2021df_codec_breakdown as R21
@@ -655,6 +673,8 @@ def main_():
         gen_data(ref_src)
     if want("eval"):
         gen_eval(args.ref)
+    if want("eval_scores"):
+        gen_eval_scores(args.ref)
     if want("eval21"):
         gen_eval21(ref_src)
     if want("train") or want("scorefile"):

@@ -1,14 +1,12 @@
 """The oracle (CPU restatement) against golden vectors produced by the reference itself
 (tests/golden/make_golden.py). CPU only."""
 import hashlib
-import os
 import random
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REFERENCE, reference_present
 from seeded import seeded_fill_
 
 from oracle import data as odata
@@ -128,15 +126,17 @@ def test_eer_subsample(golden):
         assert oeval.compute_eer_minflip(s["bona"], s["spoof"]) == pytest.approx(s["minflip_pct"], abs=1e-12)
 
 
-@pytest.mark.skipif(not reference_present(), reason="reference score files only in the build container")
 def test_eer_b01_b02_known_answers(golden):
+    """The reference's two baseline score files, stored as data (eval_scores.npz: scores in millionths, as the
+    files print them, and the bonafide flags, in file order)."""
     g = golden("eval_golden.json")
+    sc = golden("eval_scores.npz")
     for name, expect_pct in [("B01", 9.572028), ("B02", 8.089825)]:
-        path = os.path.join(REFERENCE, f"tDCF_python_v2/scores/{name}_LA_primary_eval.txt")
+        is_bona = sc[f"{name}_bonafide"]
+        assert (int(is_bona.sum()), int((~is_bona).sum())) == (g[name]["n_bona"], g[name]["n_spoof"])
         bona, spoof = [], []
-        for ln in open(path):
-            p = ln.split()
-            (bona if p[4] == "bonafide" else spoof).append(float(p[5]))
+        for m, b in zip(sc[f"{name}_score_micro"].tolist(), is_bona.tolist()):
+            (bona if b else spoof).append(m / 1e6)
         eer, _ = oeval.compute_eer(bona, spoof)
         assert eer == g[name]["eer"]
         assert round(eer * 100, 6) == expect_pct

@@ -10,5 +10,5 @@ timeout -k 10 300 python -u tools/bench_fe.py > $O/bench_fe.jsonl 2> $O/bench_fe
 cat $O/bench_fe.jsonl
 timeout -k 10 300 python -u tools/diag_window_groups.py > $O/diag_window.jsonl 2> $O/diag_window.err
 cat $O/diag_window.jsonl
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python3 -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print('value', d['value'], 'ms/step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'mfma', d['step_mfma_frac'])"

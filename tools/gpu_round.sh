@@ -7,6 +7,7 @@ mkdir -p gpurun_out/$TAG
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$TAG/smoke.log 2>&1; rc=$?
 tail -1 gpurun_out/$TAG/smoke.log
 [ $rc -eq 0 ] || exit $rc
+BENCH_ARGS="--full ${BENCH_ARGS}"       # the round's line: roofline, kernel tables, CPU baseline
 timeout -k 10 600 python bench.py ${BENCH_ARGS} > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err; rc=$?
 cat gpurun_out/$TAG/bench.json
 [ $rc -eq 0 ] || exit $rc
