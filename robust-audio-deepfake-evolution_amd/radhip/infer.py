@@ -116,8 +116,17 @@ def produce_evaluation_file_sharded(dataset, model, device, save_path, trial_pat
     lo, hi = shard_bounds(n, world, rank)
     batches = batches or _item_batches(dataset, batch_size)
     local = []
-    for xb, _ in batches(lo, hi, device):
-        local.append(_scores(model, xb, criterion, amp).float())
+    if amp == "x3":
+        # the weight planes of the x3 stream are a cache: a pass never starts from those of an earlier pass (a
+        # write through p.data or a raw pointer in between is invisible to their key), nor keeps them afterwards
+        from . import wavlm_x3
+        wavlm_x3.drop(model)
+    try:
+        for xb, _ in batches(lo, hi, device):
+            local.append(_scores(model, xb, criterion, amp).float())
+    finally:
+        if amp == "x3":
+            wavlm_x3.drop(model)
     local = torch.cat(local) if local else torch.zeros(0, device=device)
     if world > 1:
         width = shard_bounds(n, world, 0)[1]

@@ -99,6 +99,9 @@ class AdamW(torch.optim.AdamW):
         found_inf = getattr(self, "found_inf", None)
         if not hasattr(self, "_tables"):
             self._tables = {}
+        # the kernel writes through raw pointers, which no version counter sees: the x3 scoring planes are stale
+        from .wavlm_x3 import invalidate
+        invalidate()
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:

@@ -21,7 +21,7 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, ops, wavlm_x3
 from .augment import CODEC_RATES, draw_rawboost
 from .ops import add_many, fgm_attack, pad_mixup, rawboost_batch, resample_batch, resample_kernel
 from .wavlm import compute_time_mask
@@ -99,6 +99,7 @@ class FGM:
         return [(n, p) for n, p in self.model.named_parameters() if p.requires_grad and self.emb_name in n]
 
     def attack(self):
+        wavlm_x3.invalidate()             # p.data writes: no version counter moves
         tg = self._targets()
         with_grad = [(n, p) for n, p in tg if p.grad is not None]
         for n, p in tg:
@@ -116,7 +117,8 @@ class FGM:
             self.backup[n] = b
 
     def restore(self):
-        pairs = [(p.data, self.backup[n]) for n, p in self.model.named_parameters()
+        wavlm_x3.invalidate()
+        pairs =[(p.data, self.backup[n]) for n, p in self.model.named_parameters()
                  if p.requires_grad and self.emb_name in n and n in self.backup]
         if pairs and all(d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and b.is_contiguous()
                          for d, b in pairs):
@@ -165,6 +167,7 @@ class EMA:
         """Exchange live and EMA values (call twice to restore)."""
         if self.shadow is None:
             return
+        wavlm_x3.invalidate()             # p.data writes: no version counter moves
         params = dict(self.model.named_parameters())
         bufs = dict(self.model.named_buffers())
         for n, s in list(zip(self.names, self.shadow)) + list(zip(self.buf_names, self.buffers)):

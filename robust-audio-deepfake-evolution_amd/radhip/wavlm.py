@@ -88,7 +88,11 @@ def _compute_dtype(x):
 
 
 def frozen_linear(x, lin, cache):
-    """F.linear with a cached cast of a frozen nn.Linear (falls back to the live weight if trainable)."""
+    """F.linear with a cached cast of a frozen nn.Linear (falls back to the live weight if trainable). A LoraLinear's
+    `weight` / `bias` are its base layer's, so an active adapter's part is added here."""
+    if isinstance(lin, LoraLinear):
+        y = frozen_linear(x, lin.base_layer, cache)
+        return y + lin.delta(x).to(y.dtype) if lin.active else y
     w, b = lin.weight, lin.bias
     if w.requires_grad or (b is not None and b.requires_grad):
         return F.linear(x, w, b)

@@ -13,11 +13,30 @@ per product against fp32's 2^-24, at a third of the bf16 MFMA rate. The rest of 
   * per layer: LN1 + gate -> planes; q|k|v x3 GEMM -> fp32; fp32 gated attention (v_mfma_f32_16x16x4_f32) -> planes;
     out_proj x3 -> fp32; residual + LN2 -> planes; FFN1 + GELU x3 (planes out) -> FFN2 x3 -> fp32; the residual
     add runs in the next layer's LN1 pass.
-The frozen weights' planes are made once per weight version (LoRA in "active" mode merged into q / v first:
-W + s B A, the same product the adapter adds). Everything else of the model (SincNet, fusion, Bi-Mamba, head) runs
-its fp32 kernels.
+Everything else of the model (SincNet, fusion, Bi-Mamba, head) runs its fp32 kernels.
 
 Enabled by `scoring()` (radhip.infer._scores with amp="x3"); RADHIP_X3=0 disables it.
+
+Adapters. Every Linear of the stream is read through `_merged`: an active LoRA adapter (q / k / v / out_proj in
+lora_mode "active"; feature_projection.projection, gru_rel_pos_linear, intermediate_dense and output_dense in both
+modes, radhip.wavlm.inject_lora) enters the planes as W + s B A, the product the adapter adds in eval (no dropout).
+An inactive adapter is left out, as the module path leaves it out. An active adapter on any other module is not
+merged, and `eligible()` then refuses the stream, so the module path scores.
+
+Shapes. `eligible()` computes the token count T from the conv stack and takes 1 <= T <= 256 (400 <= L < 82320 for
+WavLM-Large), the range of rdx_x3_attn_fwd; a longer input takes the module path.
+
+When the planes are rebuilt. The planes (`_x3w` on the WavLM model) are a cache of the weights, keyed on
+  * `data_ptr` and `_version` of every parameter and buffer: `load_state_dict`, `copy_`, any in-place op on the
+    parameter itself;
+  * the module-wide epoch that `invalidate()` advances. The writers that bypass a parameter's version counter call
+    it: radhip.optim.AdamW.step (raw pointers), radhip.train.EMA.swap and FGM.attack / FGM.restore (`p.data`).
+A foreign write through `p.data` or a raw pointer (a captured graph replaying an optimizer step, another
+optimizer) changes neither, so `radhip.infer.produce_evaluation_file_sharded`, the entry of every scoring pass of
+the trainer, calls `drop(model)` before its first batch and after its last: a pass never starts from planes of an
+earlier pass, and the planes (about 1.3 GB for WavLM-Large) are not resident between passes. Within a pass, and
+between direct `_scores` calls with nothing changed, the same X3Weights object is reused. A caller that writes
+weights behind all of these between two direct `_scores` calls has to call `invalidate()` itself.
 """
 import contextlib
 import os
@@ -30,6 +49,7 @@ from ._lib import check, lib
 from .ops import _p, _stream, _timed, gemm_flops, rel_bias_table, _wgemm_workspace
 
 _STATE = threading.local()
+_EPOCH = [0]                      # advanced by invalidate(): part of every cached X3Weights' key
 
 # (tile, splits, group_m) of rdx_hgemm_x3 per GEMM at the eval batch (32 x 201 tokens), from the standalone sweep
 # (tools/bench_x3.py, profiles/r06_bench_x3.jsonl, us; bf16-equivalent rate / 2.5 PF): q|k|v 256 x 192 column order
@@ -54,6 +74,25 @@ def active():
     return getattr(_STATE, "on", False) and os.environ.get("RADHIP_X3", "1") != "0"
 
 
+def invalidate():
+    """Weights were written in a way the parameters' version counters do not see (raw pointers, `p.data`): every
+    cached X3Weights is rebuilt at its next use."""
+    _EPOCH[0] += 1
+
+
+def drop(model):
+    """Free the cached planes of every WavLM stream inside `model`."""
+    for m in model.modules():
+        m.__dict__.pop("_x3w", None)
+
+
+def tokens(c, L):
+    """Frames the conv stack of config `c` makes of L samples (0: too short)."""
+    for k, s in zip(c.conv_kernel, c.conv_stride):
+        L = (L - k) // s + 1 if L >= k else 0
+    return L
+
+
 def planes(w):
     """fp32 tensor -> (hi, lo) bf16 tensors of its shape: hi = bf16(w), lo = bf16(w - hi)."""
     w = w.detach().float()
@@ -64,7 +103,8 @@ def planes(w):
 
 def eligible(model, x):
     """The x3 stream applies to WavLM-Large geometry (layer-norm CNN of 512 channels with conv0 k 10, stable layer
-    norm, 64-dim heads, GELU FFN, the 128-tap / 16-group positional conv), CUDA, eval mode, no grad."""
+    norm, 64-dim heads, GELU FFN, the 128-tap / 16-group positional conv), 1 to 256 tokens, CUDA, eval mode, no grad,
+    and no active adapter outside the Linears that `_merged` folds into the planes."""
     c = model.config
     if not (active() and x.is_cuda and x.dim() == 2 and not model.training and not torch.is_grad_enabled()):
         return False
@@ -74,15 +114,22 @@ def eligible(model, x):
     ok = (c.feat_extract_norm == "layer" and c.feat_extract_activation == "gelu" and c.hidden_act == "gelu"
           and all(d == 512 for d in c.conv_dim) and c.conv_kernel[0] == 10 and c.conv_dim[0] == 512
           and c.do_stable_layer_norm and c.hidden_size == 1024 and c.hidden_size // c.num_attention_heads == 64
-          and c.num_conv_pos_embeddings == 128 and c.num_conv_pos_embedding_groups == 16 and x.shape[1] >= 400)
+          and c.num_conv_pos_embeddings == 128 and c.num_conv_pos_embedding_groups == 16
+          and 1 <= tokens(c, x.shape[1]) <= 256)
     if not ok:
         return False
+    merged = {id(m) for m in _linears(model)}
+    return not any(isinstance(m, LoraLinear) and m.active and id(m) not in merged for m in model.modules())
+
+
+def _linears(model):
+    """The Linears X3Weights reads through `_merged`."""
+    out = [model.feature_projection.projection]
     for layer in model.encoder.layers:
-        a = layer.attention
-        for name in ("k_proj", "out_proj"):
-            if isinstance(getattr(a, name), LoraLinear) and getattr(a, name).active:
-                return False
-    return True
+        a, ff = layer.attention, layer.feed_forward
+        out += [a.q_proj, a.k_proj, a.v_proj, a.out_proj, a.gru_rel_pos_linear, ff.intermediate_dense,
+                ff.output_dense]
+    return out
 
 
 def _merged(lin):
@@ -99,9 +146,10 @@ def _merged(lin):
 
 
 def _src(model):
-    """Every tensor the planes are made from (weights, LoRA factors) with its version: the cache key."""
+    """The cache key: the epoch of `invalidate()`, and every tensor the planes are made from (weights, LoRA
+    factors) with its version."""
     ts = [p for p in model.parameters()] + [b for b in model.buffers()]
-    return tuple((t.data_ptr(), t._version) for t in ts)
+    return (_EPOCH[0],) + tuple((t.data_ptr(), t._version) for t in ts)
 
 
 class X3Weights:
@@ -122,8 +170,8 @@ class X3Weights:
                 self.fe.append((planes(w), f(ly.conv.bias), f(ly.layer_norm.weight), f(ly.layer_norm.bias),
                                 float(ly.layer_norm.eps), ly.conv.kernel_size[0], ly.conv.stride[0]))
             fp = model.feature_projection
-            self.fp = (f(fp.layer_norm.weight), f(fp.layer_norm.bias), float(fp.layer_norm.eps),
-                       planes(fp.projection.weight), f(fp.projection.bias))
+            wp, bp = _merged(fp.projection)
+            self.fp = (f(fp.layer_norm.weight), f(fp.layer_norm.bias), float(fp.layer_norm.eps), planes(wp), f(bp))
             pce = model.encoder.pos_conv_embed
             W = pce._weight().detach().float().reshape(16, 64, 64, 128)                 # [g, n, c, k]
             wk = W.permute(0, 3, 1, 2).contiguous()                                     # [g][k][n][c]
@@ -133,16 +181,16 @@ class X3Weights:
                 a, ff = layer.attention, layer.feed_forward
                 (wq, bq), (wk_, bk), (wv, bv) = _merged(a.q_proj), _merged(a.k_proj), _merged(a.v_proj)
                 wo, bo = _merged(a.out_proj)
+                (wg, bg), (w1, b1), (w2, b2) = (_merged(a.gru_rel_pos_linear), _merged(ff.intermediate_dense),
+                                                _merged(ff.output_dense))
                 self.layers.append(dict(
                     ln1=(f(layer.layer_norm.weight), f(layer.layer_norm.bias), float(layer.layer_norm.eps)),
-                    gate=(f(a.gru_rel_pos_linear.weight), f(a.gru_rel_pos_linear.bias),
-                          f(a.gru_rel_pos_const.reshape(-1))),
+                    gate=(f(wg), f(bg), f(a.gru_rel_pos_const.reshape(-1))),
                     wqkv=planes(torch.cat([wq, wk_, wv])), bqkv=f(torch.cat([bq, bk, bv])),
                     wo=planes(wo), bo=f(bo),
                     ln2=(f(layer.final_layer_norm.weight), f(layer.final_layer_norm.bias),
                          float(layer.final_layer_norm.eps)),
-                    w1=planes(ff.intermediate_dense.weight), b1=f(ff.intermediate_dense.bias),
-                    w2=planes(ff.output_dense.weight), b2=f(ff.output_dense.bias)))
+                    w1=planes(w1), b1=f(b1), w2=planes(w2), b2=f(b2)))
             ln = model.encoder.layer_norm
             self.ln_f = (f(ln.weight), f(ln.bias), float(ln.eps))
             self.rel_emb = model.encoder.layers[0].attention

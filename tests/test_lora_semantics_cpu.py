@@ -8,6 +8,7 @@ restated (oracle/model.py::OLoraLinear, parity of peft itself unpinned); transfo
 one. With non-zero adapters the outputs stay the base model's and the adapters get no gradient, which is what
 the product's default lora_mode "reference" reproduces (radhip.wavlm.LoraLinear active=False; radhip.train
 leaves such weights out of the gradient buffer, as AdamW skips parameters without .grad)."""
+import copy
 import json
 
 import numpy as np
@@ -117,3 +118,32 @@ def test_reference_mode_bypasses_only_the_attention_projections():
     wrapped2, _ = inject_lora(Layer(), r=2, alpha=4, dropout=0.0, targets=targets, active=True)
     layer2 = wrapped2.model if hasattr(wrapped2, "model") else next(iter(wrapped2.children()))
     assert layer2.attention.q_proj.active and layer2.feed_forward.intermediate_dense.active
+
+
+def test_module_path_applies_active_adapters_on_cached_linears():
+    """The FFN and out_proj go through frozen_linear, which reads `.weight` / `.bias`: on a LoraLinear those are the
+    base layer's, so the adapter's part has to be added there (an active one) or left out (a bypassed one)."""
+    import torch.nn.functional as F
+    from radhip.wavlm import FeedForward, LoraLinear, WavLMConfigLite
+    torch.manual_seed(0)
+    ff = FeedForward(WavLMConfigLite(hidden_size=16, intermediate_size=32)).double().eval().requires_grad_(False)
+    x = torch.randn(3, 5, 16, dtype=torch.float64)
+    base = ff(x)
+    for active in (True, False):
+        f2 = copy.deepcopy(ff)
+        for name in ("intermediate_dense", "output_dense"):
+            lin = LoraLinear(getattr(f2, name), 2, 4, 0.0, active=active).double()
+            with torch.no_grad():
+                lin.lora_B["default"].weight.normal_()
+            setattr(f2, name, lin)
+        w = []
+        for lin in (f2.intermediate_dense, f2.output_dense):
+            w.append(lin.base_layer.weight + 2.0 * lin.lora_B["default"].weight @ lin.lora_A["default"].weight)
+        want = F.linear(F.gelu(F.linear(x, w[0], f2.intermediate_dense.bias)), w[1], f2.output_dense.bias)
+        with torch.no_grad():
+            got = f2(x)
+        if active:
+            torch.testing.assert_close(got, want, rtol=0, atol=1e-12)
+            assert float((got - base).abs().max()) > 1e-2
+        else:
+            torch.testing.assert_close(got, base, rtol=0, atol=0)

@@ -209,24 +209,53 @@ def test_x3_feature_encoder_matches_fp64():
 
 
 # ------------------------------------------------------------------------------------------ whole model ----------
-def _model_and_oracle(lora_mode):
+def _oracle_state(m, adapters=None):
+    """The product model's state as a LoRA-free oracle's, in fp64: every adapter the forward applies folded into its
+    Linear as W + s B A (peft's lora.Linear in eval: y = W x + b + s B A x), every bypassed one left out.
+    adapters True / False folds all / none of them whatever their mode."""
+    from radhip.wavlm import LoraLinear
+    sd = {k: v.detach().double() for k, v in m.state_dict().items()}
+    for name, mod in m.named_modules():
+        if not isinstance(mod, LoraLinear):
+            continue
+        a = mod.adapter
+        w = sd.pop(f"{name}.base_layer.weight")
+        A, B = sd.pop(f"{name}.lora_A.{a}.weight"), sd.pop(f"{name}.lora_B.{a}.weight")
+        if mod.active if adapters is None else adapters:
+            w = w + mod.scaling[a] * (B @ A)
+        sd[f"{name}.weight"] = w
+        sd[f"{name}.bias"] = sd.pop(f"{name}.base_layer.bias")
+    return {k.replace("wavlm_stream.model.base_model.model.", "wavlm_stream.model."): v for k, v in sd.items()}
+
+
+def _model_and_oracle(lora_mode, depth=24, targets=None, lora_std=0.02):
+    """The Phase-6 model and its fp64 oracle. targets None: Phase 6's own q / v adapters, mirrored by the oracle's
+    LoRA layers. A list: those lora_target_modules ([]: no LoRA, the stream left trainable) against a LoRA-free
+    oracle that `_oracle_state` fills (reload it with o.load_state_dict(_oracle_state(m)) after a weight change)."""
     from oracle.model import OracleModel, apply_lora, from_peft_state
     from radhip.build import apply_lora_to_wavlm, get_model, load_config
     from radhip.wavlm import WAVLM_LARGE
     cfg = load_config("Phase6_Proposed.conf")
     cfg["training_config"]["lora_mode"] = lora_mode
-    w = dict(WAVLM_LARGE)
+    if targets is not None:
+        cfg["training_config"]["use_lora"] = bool(targets)
+        cfg["training_config"]["lora_target_modules"] = list(targets)
+    w = dict(WAVLM_LARGE, num_hidden_layers=depth)
     cfg["model_config"] = dict(cfg["model_config"], wavlm_config=w)
     torch.manual_seed(1234)
     m = apply_lora_to_wavlm(get_model(cfg["model_config"], DEV), cfg["training_config"])
     with torch.no_grad():           # peft initialises lora_B to zero: give the adapters a part to play
         for n, p in m.named_parameters():
             if "lora_B" in n:
-                p.normal_(0, 0.02)
+                p.normal_(0, lora_std)
     m.eval()
     ocfg = dict(w)
     ocfg["conv_dim"] = tuple(ocfg["conv_dim"])
     o = OracleModel(ocfg, emb_size=144, num_encoders=4)
+    if targets is not None:
+        o = o.double().to(DEV).eval()
+        o.load_state_dict(_oracle_state(m), strict=True)
+        return m, o
     apply_lora(o, merged=(lora_mode == "active"))
     o.load_state_dict(from_peft_state({k: v.detach().cpu() for k, v in m.state_dict().items()}), strict=True)
     return m, o.double().to(DEV).eval()
