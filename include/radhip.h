@@ -591,6 +591,29 @@ int rdx_x3_fe_conv0(const float* x, int64_t batch, int64_t len, const float* w, 
 int rdx_x3_fe_ln_gelu(const float* in, int64_t rows, const float* bias, const float* gamma, const float* beta,
                       float eps, void* out_hi, void* out_lo, float* out32, void* stream);
 
+/* ---- The SincNet stream of the fp32 scoring pass on the x3 planes (csrc/sconv_x3.hip; libradhip.so only) ----------
+ * SincNetEncoder's residual stack (src/models/DualStreamSEMamba.py:144-270) in eval mode with frozen BatchNorm, no
+ * backward. Activations are fp32 NHWC and are split into planes while they are staged; convolution weights are the
+ * bf16 planes of the fp32 weight, tap-major [kh * 3 + kw][co][ci]; every product of the 32 / 64-channel convolutions
+ * is x_hi w_hi + x_lo w_hi + x_hi w_lo on the bf16 MFMA with fp32 accumulation. BN tables are bn fp32 [4][C] = (conv
+ * bias, running mean, invstd * gamma, beta).
+ *   rdx_x3_b0x_fwd: block 0 in one pass, y = MaxPool2d((1,3))(conv2(selu(bn2(conv1(x) + b1))) + conv_downsample(x) +
+ *     bias), fp32 NHWC [N, H, W / 3, 32]. x fp32 [N, H, W] (one channel); fbn fp32 [2] = (scale, shift) of the
+ *     encoder's first_bn: the kernel then reads the raw SincConv output and applies selu(x * scale + shift) as it
+ *     stages x; NULL: x is already activated. w1 fp32 [32][6] (conv1, tap kh * 3 + kw), wd fp32 [32][3]
+ *     (conv_downsample), both on the fp32 VALU; bn [4][32] of conv1 / bn2; w2_hi / w2_lo [6][32][32] (conv2); bias
+ *     fp32 [32] = conv2.bias + conv_downsample.bias. W < 3: RDX_EUNSUPPORTED.
+ *   rdx_x3_sconv_fwd: y fp32 NHWC [N, H + 2 ph - kh + 1, W, co] = conv2d(x fp32 NHWC [N, H, W, ci], kernel kh x 3,
+ *     padding (ph, 1)) without bias (bn == NULL: conv2, conv_downsample; the bias enters rdx_res_tail_fwd), or
+ *     selu(bn(acc + conv bias)) with bn [4][co] (conv1). ci, co in {32, 64}, kh in {1, 2}, ph in {0, 1}, at least one
+ *     output row; anything else RDX_EUNSUPPORTED. y must not alias x.
+ * NULL pointers: RDX_EINVAL. Every check returns before any device work. */
+int rdx_x3_b0x_fwd(const float* x, const float* fbn, const float* w1, const float* wd, const float* bn,
+                   const void* w2_hi, const void* w2_lo, const float* bias, float* y, int N, int H, int W,
+                   void* stream);
+int rdx_x3_sconv_fwd(const float* x, const void* w_hi, const void* w_lo, const float* bn, float* y, int N, int H,
+                     int W, int ci, int co, int kh, int ph, void* stream);
+
 /* Column sums of fp32 row-partial buffers, up to 4 problems per launch: out_k[c] = sum_r in_k[r * ld_k + c] (rows
  * in order, fixed-order combine: deterministic). Replaces the torch reductions of the scan / depthwise-conv backward
  * partials (csrc/layersum.hip). */

@@ -521,7 +521,9 @@ def parse_args(argv=None):
                         help="scoring precision: x3 (default), the reference's fp32 scoring (src/main.py:958-995, no "
                              "autocast) with the WavLM stream on the hand-written split-precision kernels "
                              "(radhip/wavlm_x3.py: bf16 hi/lo planes, three MFMA products per GEMM, fp32 attention; "
-                             "scores within 2e-6 of fp32, 2.2x its rate: tools/bench_eval.py); fp32, the same forward "
+                             "scores within 2e-6 of fp32, 2.2x its rate: tools/bench_eval.py; and the SincNet stream on "
+                             "split-precision convolutions, radhip/sinc_x3.py: 26.0 against 33.0 ms per batch of 32 "
+                             "with RADHIP_X3_SINC=0, tools/bench_sinc_x3.py); fp32, the same forward "
                              "with the WavLM stream on torch SDPA + hipBLASLt fp32; or bf16 / fp16 autocast, which "
                              "runs the hand-written HIP encoder / SincNet path (tools/bench_eval.py: throughput and "
                              "score deviation). 16-bit scores are parity-unpinned against the reference (no fixture "

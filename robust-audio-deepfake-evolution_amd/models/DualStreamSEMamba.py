@@ -23,6 +23,7 @@ from radhip.head import attn_pool, pool_eligible, se_eligible, se_layer, upcat, 
 from radhip.linear import RowLayerNorm, SideLinear, ffn_residual
 from radhip.mamba import Mamba
 from radhip.ops import layer_weighted_sum
+from radhip import sinc_x3
 from radhip.sinc import CONV, Residual_block, SincNetEncoder  # noqa: F401  (re-exported like the reference)
 from radhip.wavlm import PeftWrapped, WavLMConfigLite, WavLMEncoderModel
 
@@ -239,6 +240,8 @@ class Model(nn.Module):
         side = _side_stream(x)
         if Freq_aug and self.sinc_stream.conv_time.mask_dev is None:
             side = None
+        if side is not None and sinc_x3.eligible(self.sinc_stream, x, Freq_aug):
+            side = None                      # the x3 scoring pass runs its two streams in order (radhip/sinc_x3.py)
         if side is None:
             return self.wavlm_stream(x), self.sinc_stream(x, freq_aug=Freq_aug)
         cur = torch.cuda.current_stream(x.device)

@@ -213,6 +213,8 @@ SIGNATURES = {
     "rdx_x3_posconv_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "rdx_x3_fe_conv0": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, c_int, c_int, c_vp, c_vp, c_vp]),
     "rdx_x3_fe_ln_gelu": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "rdx_x3_b0x_fwd": (c_int, [c_vp] * 9 + [c_int, c_int, c_int, c_vp]),
+    "rdx_x3_sconv_fwd": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp]),
     "rdx_fgm_attack": (c_int, [c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                ctypes.POINTER(c_i64), c_f32, c_vp, c_vp]),
 }

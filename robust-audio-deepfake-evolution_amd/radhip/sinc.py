@@ -12,6 +12,7 @@ import torch.nn as nn
 
 import torch.nn.functional as F
 
+from . import sinc_x3
 from .ops import (HALF, Block0Convs, Block0Front, Block0Fused, BnSelu, ResBlockIdentity, BnSeluSConv, ResTail, SConv, SConvBnSelu, SConvBnSeluSConv, sconv_ok,
                   sconv_weight_ok, sincconv_absmaxpool)
 
@@ -223,6 +224,9 @@ class SincNetEncoder(nn.Module):
 
     def forward(self, x, freq_aug=False):
         """x [B, T] -> e_T [B, T', 64] (SincNetEncoder.forward :238-270)."""
+        if sinc_x3.eligible(self, x, freq_aug):
+            # the fp32 scoring pass on the split-precision kernels (radhip/sinc_x3.py)
+            return sinc_x3.forward(self, x)
         x = self.conv_time.absmaxpool(x.float(), mask=freq_aug).unsqueeze(1)    # [B, 1, 23, T/3]
         x = self.selu(self.first_bn(x))
         if self.channels_last and x.is_cuda:

@@ -13,7 +13,9 @@ per product against fp32's 2^-24, at a third of the bf16 MFMA rate. The rest of 
   * per layer: LN1 + gate -> planes; q|k|v x3 GEMM -> fp32; fp32 gated attention (v_mfma_f32_16x16x4_f32) -> planes;
     out_proj x3 -> fp32; residual + LN2 -> planes; FFN1 + GELU x3 (planes out) -> FFN2 x3 -> fp32; the residual
     add runs in the next layer's LN1 pass.
-Everything else of the model (SincNet, fusion, Bi-Mamba, head) runs its fp32 kernels.
+The SincNet stream has x3 kernels of its own (radhip/sinc_x3.py, csrc/sconv_x3.hip; RADHIP_X3_SINC=0 keeps its fp32
+module path) and then runs after this stream, in order. The rest of the model (fusion, Bi-Mamba, head) runs its fp32
+kernels.
 
 Enabled by `scoring()` (radhip.infer._scores with amp="x3"); RADHIP_X3=0 disables it.
 
