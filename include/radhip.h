@@ -721,6 +721,30 @@ int rdx_sconv_fwd_res(const void* x, const void* w, void* y, const void* res, in
  * bn = [cb | mean | invstd*gamma | beta | invstd] (5 x co fp32); sums zeroed by the caller. */
 int rdx_sconv_dgrad_bnselu(const void* dy, const void* w, const void* c, void* dc, const float* bn, float* sums,
                            int N, int H, int W, int ci, int co, int kh, int ph, void* stream);
+/* The residual block's max-pool without its full-width tensors (blocks 1-5; W >= 3, anything else
+ * RDX_EUNSUPPORTED). A pooled gradient is the pair (dp [.., W/3, c] 16-bit, arg [.., W/3, c] window index bytes)
+ * standing for rdx_res_tail_bwd's full-width scatter ds[w] = arg[w/3] == w%3 ? dp[w/3] : 0 (0 for w >= 3 (W/3)).
+ *   rdx_sconv_fwd_pool: y [N, H-1, W/3, c] = MaxPool2d((1, 3))(bf16(conv2(x)) + idn + bias) and arg — rdx_sconv_fwd
+ *     (kh 2, ph 0, ci = co = c in {32, 64}) then rdx_res_tail_fwd, bit for bit; idn [N, H-1, W, c], bias fp32 [c].
+ *   rdx_sconv_fwd_res_pool: rdx_sconv_fwd_res (kh 2, ci = co in {32, 64}) with res given as a pooled gradient
+ *     [N, Ho, W/3, co]; dbias [co] += the per-channel sum of dp, rdx_res_tail_bwd's bias gradient (fp32 atomics;
+ *     zeroed by the caller).
+ *   rdx_sconv_dgrad_bnselu_pool: rdx_sconv_dgrad_bnselu with dy given as a pooled gradient [N, H, W/3, ci].
+ *   rdx_sconv_wgrad_pool: rdx_sconv_wgrad (kh 2, ci = co in {32, 64}; or block 2's conv_downsample, kh 1, 32 -> 64)
+ *     with dy given as a pooled gradient [N, Ho, W/3, co].
+ *   rdx_sconv_dgrad_pool: the input gradient of block 2's conv_downsample, rdx_sconv_fwd (ci 64, co 32, kh 1, ph 0,
+ *     w the flipped kernel [3][32][64]) on a pooled gradient [N, H, W/3, 64]; dx [N, H, W, 32]. */
+int rdx_sconv_fwd_pool(const void* x, const void* w, const void* idn, const float* bias, void* y, uint8_t* arg, int N,
+                       int H, int W, int ci, int co, void* stream);
+int rdx_sconv_fwd_res_pool(const void* x, const void* w, void* y, const void* dp, const uint8_t* arg, float* dbias,
+                           int N, int H, int W, int ci, int co, int kh, int ph, void* stream);
+int rdx_sconv_dgrad_bnselu_pool(const void* dp, const uint8_t* arg, const void* w, const void* c, void* dc,
+                                const float* bn, float* sums, int N, int H, int W, int ci, int co, int kh, int ph,
+                                void* stream);
+int rdx_sconv_dgrad_pool(const void* dp, const uint8_t* arg, const void* w, void* dx, int N, int H, int W, int ci,
+                         int co, int kh, int ph, void* stream);
+int rdx_sconv_wgrad_pool(const void* x, const void* dp, const uint8_t* arg, float* dw, float* part, int N, int H,
+                         int W, int ci, int co, int kh, int ph, void* stream);
 int rdx_sconv_wgrad_nblk(int N, int Ho, int W);
 int rdx_sconv_wgrad(const void* x, const void* dy, float* dw, float* part, int N, int H, int W, int ci, int co,
                     int kh, int ph, void* stream);

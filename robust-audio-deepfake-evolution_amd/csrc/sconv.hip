@@ -15,7 +15,10 @@
 // operand), so a lane holds one position and groups of 4 consecutive channels: 8-byte stores.
 // Epilogue options: bf16 output (no bias: the conv biases are folded into the next fused pass, as
 // radhip.ops.BnSelu / ResTail expect), or additionally the frozen-BN + SELU activation of that output (the
-// conv1 -> bn2 -> selu chain), so conv2's input is produced without another pass over HBM.
+// conv1 -> bn2 -> selu chain), so conv2's input is produced without another pass over HBM; or, for conv2 of blocks
+// 1-5, the residual sum and MaxPool2d((1, 3)) themselves (kPool: only the pooled tensor and its window index bytes
+// are written). In the backward that pool's gradient stays pooled: the kernels that consume it expand (dy, index
+// byte) to full width where they stage it (kExpIn, the weight gradient's kExp) or add it (kExpRes).
 //
 // Weight gradient: dW[co, ci, kh, kw] = sum_{n, ho, w} dY[n, ho, w, co] * X[n, ho + kh - ph, w + kw - 1, ci].
 // A workgroup walks units of (output row, 128-position strip) in a grid-stride loop, stages the dY strip and
@@ -62,7 +65,14 @@ struct SConvArgs {
                             //   backward epilogue reads a fifth row, invstd
   const hst* c;  // backward epilogue: the saved pre-activation [N, Ho, W, CO]
   float* sums;              // backward epilogue: [3][CO] d conv_bias | d gamma | d beta (fp32 atomics)
-  const hst* res;  // optional [N, Ho, W, CO]: y = bf16(bf16(conv) + res) (a residual branch's gradient)
+  const hst* res;  // optional [N, Ho, W, CO]: y = bf16(bf16(conv) + res) (a residual branch's gradient);
+                   //   kPool: the identity [N, Ho, W, CO] of the residual sum
+  // A max-pool gradient kept pooled, (dp [.., W/3, C] 16-bit, arg [.., W/3, C] window index bytes): the full-width
+  // tensor it stands for is ds[w] = arg[w/3] == w%3 ? dp[w/3] : 0 for w < 3 (W/3), else 0 (rdx_res_tail_bwd's
+  // scatter), formed on the fly. xarg: x is such a pair (kExpIn); rarg: res is one ([N, Ho, W/3, CO]).
+  const uint8_t* xarg;
+  const uint8_t* rarg;
+  uint8_t* parg;   // kPool: the pooled output's window index bytes [N, Ho, W/3, CO] (y is [N, Ho, W/3, CO])
   int N, H, W, Ho, ph;
   int rows_per;             // output rows per workgroup (grid.z chunks of the Ho rows)
 };
@@ -81,26 +91,68 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t sc_rsrc(const void* p, int64_t
 // one unconditional buffer load per 16-byte item (an item outside the image gets an offset past the range and
 // loads 0). Branch-free, so the compiler tracks the loads exactly and does not wait on them, or on the stores
 // around them, before they are used.
-template <int CI>
+template <int CI, int PW = SC_PW>
 __device__ __forceinline__ void sc_load_row(uint4* regs, __amdgpu_buffer_rsrc_t rs, int hi, int H, int W, int p0) {
+  constexpr int XCH = CI / 8, NV = (PW * XCH + SC_T - 1) / SC_T;
+  const bool rok = hi >= 0 && hi < H;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int i = threadIdx.x + SC_T * j;
+    const int ch = i % XCH, pp = i / XCH, wi = p0 - 1 + pp;
+    const bool ok = rok && pp < PW && wi >= 0 && wi < W;
+    const uint32_t off = ok ? (uint32_t)(((hi * W + wi) * CI + ch * 8) * 2) : SC_OOB;
+    regs[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+  }
+}
+template <int CI, int PW = SC_PW>
+__device__ __forceinline__ void sc_store_row(char* slot, const uint4* regs) {
+  constexpr int XCH = CI / 8, NV = (PW * XCH + SC_T - 1) / SC_T;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int i = threadIdx.x + SC_T * j;
+    if (i < PW * XCH) *reinterpret_cast<uint4*>(slot + sc_off<CI>(i / XCH, i % XCH)) = regs[j];
+  }
+}
+
+// Eight elements of a pooled gradient (d: 16-bit values, ab: their window index bytes) as they stand at column
+// 3 wo + j of the full-width tensor: the value where the index is j, +0 elsewhere (rdx_res_tail_bwd's scatter).
+__device__ __forceinline__ uint32_t sc_exp2(uint32_t d, uint32_t ab, uint32_t j) {
+  return d & (((ab & 0xffu) == j ? 0xffffu : 0u) | (((ab >> 8) & 0xffu) == j ? 0xffff0000u : 0u));
+}
+__device__ __forceinline__ uint4 sc_expand(uint4 d, uint2 ab, uint32_t j) {
+  return make_uint4(sc_exp2(d.x, ab.x, j), sc_exp2(d.y, ab.x >> 16, j), sc_exp2(d.z, ab.y, j),
+                    sc_exp2(d.w, ab.y >> 16, j));
+}
+
+// sc_load_row / sc_store_row for an input row that is a pooled gradient (rs over [H, Wo, CI] 16-bit, ra over its
+// index bytes): the raw pooled items are loaded (still branch-free; a column past 3 Wo loads 0) and expanded only
+// when they are written to LDS, so the loads stay in flight over the row's MFMAs like the plain ones.
+template <int CI>
+__device__ __forceinline__ void sc_load_row_exp(uint4* regs, uint2* aregs, __amdgpu_buffer_rsrc_t rs,
+                                                __amdgpu_buffer_rsrc_t ra, int hi, int H, int Wo, int p0) {
   constexpr int XCH = CI / 8, NV = (SC_PW * XCH + SC_T - 1) / SC_T;
   const bool rok = hi >= 0 && hi < H;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int i = threadIdx.x + SC_T * j;
     const int ch = i % XCH, pp = i / XCH, wi = p0 - 1 + pp;
-    const bool ok = rok && pp < SC_PW && wi >= 0 && wi < W;
-    const uint32_t off = ok ? (uint32_t)(((hi * W + wi) * CI + ch * 8) * 2) : SC_OOB;
-    regs[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+    const int wo = wi / 3;   // wi >= -1: the quotient of -1 is 0, ruled out below
+    const bool ok = rok && pp < SC_PW && wi >= 0 && wo < Wo;
+    const uint32_t e = (uint32_t)((hi * Wo + wo) * CI + ch * 8);
+    regs[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? e * 2 : SC_OOB, 0, 0));
+    aregs[j] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(ra, ok ? e : SC_OOB, 0, 0));
   }
 }
 template <int CI>
-__device__ __forceinline__ void sc_store_row(char* slot, const uint4* regs) {
+__device__ __forceinline__ void sc_store_row_exp(char* slot, const uint4* regs, const uint2* aregs, int p0) {
   constexpr int XCH = CI / 8, NV = (SC_PW * XCH + SC_T - 1) / SC_T;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int i = threadIdx.x + SC_T * j;
-    if (i < SC_PW * XCH) *reinterpret_cast<uint4*>(slot + sc_off<CI>(i / XCH, i % XCH)) = regs[j];
+    const int wi = p0 - 1 + i / XCH;
+    if (i < SC_PW * XCH)
+      *reinterpret_cast<uint4*>(slot + sc_off<CI>(i / XCH, i % XCH)) =
+          sc_expand(regs[j], aregs[j], (uint32_t)((wi + 3) % 3));
   }
 }
 
@@ -108,27 +160,51 @@ __device__ __forceinline__ void sc_store_row(char* slot, const uint4* regs) {
 // the epilogue continues it through the frozen BN + SELU backward of bnselu_bwd_kernel (csrc/sincnet.hip) on the
 // bf16-rounded dO1, as the unfused path would: y = dc, and the per-channel sums of dc, dc/s * xhat, dc/s go
 // to a.sums, so dO1 never goes through HBM.
-template <int CI, int CO, int KH, bool kBnBwd = false>
+//
+// kPool: the residual block's tail in conv2's epilogue, y = MaxPool2d((1, 3))(bf16(conv) + identity + bias) and
+// the window index bytes, exactly tail_fwd_kernel (csrc/sincnet.hip) on the rounded convolution output, which is
+// never stored. A lane holds one position, so a pool window is three neighbouring lanes: each wave works on 32
+// positions that start one before a multiple of 3 and advance by 30 from wave to wave, which puts its ten whole
+// windows at lanes 1-3, 4-6, .., 13-15 and 16-18, .., 28-30 of each half-wave, inside the 16-lane DPP rows. Lane
+// 3k + 1 fetches its two right neighbours with row_shl and stores the window; lanes 0 and 31 of a half-wave only
+// recompute a neighbour wave's position. A strip is 120 positions (SC_PP), staged from one column further left.
+// kExpIn: the input x is a pooled gradient (a.x, a.xarg), expanded to full width while it is staged.
+constexpr int SC_PP = 120;          // kPool: output positions per strip (4 waves x 10 windows of 3)
+constexpr int SC_PPW = 90 + 32 + 2; // kPool: staged input positions (the last wave's 32 + halo)
+
+template <int CI, int CO, int KH, bool kBnBwd = false, bool kPool = false, bool kExpIn = false, bool kExpRes = false>
 __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
+  static_assert(!(kPool && (kBnBwd || kExpIn || kExpRes)) && !(kBnBwd && kExpRes), "one epilogue at a time");
   extern __shared__ __attribute__((aligned(16))) char sc_lds[];
-  constexpr int NSLOT = KH + 1, SLOT = SC_PW * CI * 2, XCH = CI / 8;
-  constexpr int NV = (SC_PW * XCH + SC_T - 1) / SC_T;
+  constexpr int PW = kPool ? SC_PPW : SC_PW;
+  constexpr int NSLOT = KH + 1, SLOT = PW * CI * 2, XCH = CI / 8;
+  constexpr int NV = (PW * XCH + SC_T - 1) / SC_T;
   char* ws = sc_lds;                          // [KH*3*CO][CI]
-  char* xs = sc_lds + KH * 3 * CO * CI * 2;   // NSLOT x [SC_PW][CI]
+  char* xs = sc_lds + KH * 3 * CO * CI * 2;   // NSLOT x [PW][CI]
   // the epilogue's per-channel BN parameters (up to 5 x CO fp32) in LDS: read per output element, they were
   // global loads ordered behind the previous group's stores (y may alias bn / c for the compiler)
   float* sbn = reinterpret_cast<float*>(xs + NSLOT * SLOT);
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int n = blockIdx.y, p0 = blockIdx.x * SC_P;
+  const int n = blockIdx.y, p0 = kPool ? (int)blockIdx.x * SC_PP - 1 : (int)blockIdx.x * SC_P;
   const int ho0 = blockIdx.z * a.rows_per, ho1 = min(a.Ho, ho0 + a.rows_per);
+  const int Wo = a.W / 3;   // width of the pooled tensors (kPool's output, kExpIn's input, an expanded residual)
   // buffer resources over this utterance's input and output images (the host keeps each below 2 GiB)
-  const int64_t ibytes = (int64_t)a.H * a.W * CI * 2, obytes = (int64_t)a.Ho * a.W * CO * 2;
+  const int64_t iel = (int64_t)a.H * (kExpIn ? Wo : a.W) * CI, ibytes = iel * 2;
+  const int64_t obytes = (int64_t)a.Ho * a.W * CO * 2, pel = (int64_t)a.Ho * Wo * CO;
   const int64_t obase_n = (int64_t)n * a.Ho * a.W * CO;
-  const __amdgpu_buffer_rsrc_t rx = sc_rsrc(a.x + (int64_t)n * a.H * a.W * CI, ibytes);
-  const __amdgpu_buffer_rsrc_t ry = sc_rsrc(a.y + obase_n, obytes);
-  const __amdgpu_buffer_rsrc_t ry2 = sc_rsrc(a.y2 ? a.y2 + obase_n : a.y + obase_n, obytes);
-  const __amdgpu_buffer_rsrc_t rc = sc_rsrc(kBnBwd ? a.c + obase_n : a.y + obase_n, obytes);
-  const __amdgpu_buffer_rsrc_t rres = sc_rsrc(a.res ? a.res + obase_n : a.y + obase_n, obytes);
+  const __amdgpu_buffer_rsrc_t rx = sc_rsrc(a.x + (int64_t)n * iel, ibytes);
+  const __amdgpu_buffer_rsrc_t rxa = sc_rsrc(kExpIn ? a.xarg + (int64_t)n * iel : (const uint8_t*)a.x, kExpIn ? iel : 0);
+  const __amdgpu_buffer_rsrc_t ry =
+      kPool ? sc_rsrc(a.y + (int64_t)n * pel, pel * 2) : sc_rsrc(a.y + obase_n, obytes);
+  const __amdgpu_buffer_rsrc_t rpa = sc_rsrc(kPool ? a.parg + (int64_t)n * pel : (uint8_t*)a.y, kPool ? pel : 0);
+  const __amdgpu_buffer_rsrc_t ry2 = sc_rsrc(a.y2 ? a.y2 + obase_n : a.y + obase_n, a.y2 ? obytes : 0);
+  const __amdgpu_buffer_rsrc_t rc = sc_rsrc(kBnBwd ? a.c + obase_n : a.y + obase_n, kBnBwd ? obytes : 0);
+  // the residual: full width, or (a.rarg) a pooled gradient and its index bytes
+  constexpr bool rexp = kExpRes;   // a.res is a pooled gradient, a.rarg its index bytes
+  const __amdgpu_buffer_rsrc_t rres = rexp      ? sc_rsrc(a.res + (int64_t)n * pel, pel * 2)
+                                      : a.res   ? sc_rsrc(a.res + obase_n, obytes)
+                                                : sc_rsrc(a.y, 0);
+  const __amdgpu_buffer_rsrc_t rra = sc_rsrc(rexp ? a.rarg + (int64_t)n * pel : (const uint8_t*)a.y, rexp ? pel : 0);
   {  // weights: every load issued before the first LDS store (one round trip, not one per chunk)
     constexpr int NWV = (KH * 3 * CO * XCH + SC_T - 1) / SC_T;
     const __amdgpu_buffer_rsrc_t rw = sc_rsrc(a.w, (int64_t)KH * 3 * CO * CI * 2);
@@ -145,24 +221,38 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
       if (i < KH * 3 * CO * XCH) *reinterpret_cast<uint4*>(ws + sc_off<CI>(i / XCH, i % XCH)) = wr[j];
     }
   }
-  if (a.bn && (kBnBwd || a.y2))
-    for (int i = tid; i < (kBnBwd ? 5 : 4) * CO; i += SC_T) sbn[i] = a.bn[i];
+  if (a.bn && (kBnBwd || kPool || a.y2))   // kPool: one row, the bias of the residual sum
+    for (int i = tid; i < (kBnBwd ? 5 : kPool ? 1 : 4) * CO; i += SC_T) sbn[i] = a.bn[i];
   uint4 pre[NV];
+  uint2 prea[kExpIn ? NV : 1];
+  auto load_in = [&](int hi) {
+    if constexpr (kExpIn) sc_load_row_exp<CI>(pre, prea, rx, rxa, hi, a.H, Wo, p0);
+    else sc_load_row<CI, PW>(pre, rx, hi, a.H, a.W, p0);
+  };
+  auto store_in = [&](char* slot) {
+    if constexpr (kExpIn) sc_store_row_exp<CI>(slot, pre, prea, p0);
+    else sc_store_row<CI, PW>(slot, pre);
+  };
 #pragma unroll
   for (int kh = 0; kh < KH; ++kh) {
-    sc_load_row<CI>(pre, rx, ho0 + kh - a.ph, a.H, a.W, p0);
-    sc_store_row<CI>(xs + ((ho0 + kh) % NSLOT) * SLOT, pre);
+    load_in(ho0 + kh - a.ph);
+    store_in(xs + ((ho0 + kh) % NSLOT) * SLOT);
   }
   __syncthreads();
   constexpr int NT = CO / 32;
-  const int pw = wv * 32 + r;  // this lane's position within the strip (B operand row)
+  const int pw = wv * (kPool ? 30 : 32) + r;  // this lane's position within the strip (B operand row)
   const int p = p0 + pw;
-  const bool pv = p < a.W;
+  const bool pv = p >= 0 && p < a.W;
+  // kPool: this lane stores the window of positions p .. p + 2 (lanes 3k + 1 of a half-wave, whole windows only)
+  const bool wv_ok = kPool && r % 3 == 1 && r < 30 && p / 3 < Wo;
+  // an expanded residual: this lane's column of the pooled gradient and its place in the window
+  const int rwo = p / 3, rj = p - 3 * rwo;
   // kBnBwd: per-lane sums [sum][t][g][e] over the rows this workgroup walks (channel t*32 + 8g + 4h + e)
-  float bsum[kBnBwd ? 3 : 1][NT][4][4];
-  if constexpr (kBnBwd) {
+  constexpr int NSUM = kBnBwd ? 3 : kExpRes ? 1 : 0;   // kExpRes: the sum of the pooled gradient (the bias gradient)
+  float bsum[NSUM ? NSUM : 1][NT][4][4];
+  if constexpr (NSUM > 0) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 0; q < NSUM; ++q)
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -176,14 +266,26 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
     const bool more = ho + 1 < ho1;
     // the next input row (rows past the last one this workgroup needs load zeros: ho1 <= Ho keeps them in range
     // or out of the image)
-    sc_load_row<CI>(pre, rx, more ? ho - a.ph + KH : -1, a.H, a.W, p0);
+    load_in(more ? ho - a.ph + KH : -1);
     // this lane's output byte offset in the utterance (an offset past the range for a position past W: its loads
     // read 0 and its stores are dropped)
     const uint32_t orow = pv ? (uint32_t)(((ho * a.W + p) * CO + 4 * h) * 2) : SC_OOB;
     // kBnBwd: this row's saved pre-activations, loaded with the next input row (before the MFMAs), not one
-    // round trip per channel group in the epilogue; !kBnBwd with a residual: this row's residual
+    // round trip per channel group in the epilogue; !kBnBwd with a residual: this row's residual (kPool: identity)
     uint2 cres[NT][4];
-    if (kBnBwd || a.res) {
+    uint32_t cra[NT][4];   // an expanded residual's index bytes
+    if constexpr (rexp) {
+      // element offset of this lane's 4 channels in the pooled gradient (a column past 3 Wo: out of range, 0)
+      const uint32_t erow = pv && rwo < Wo ? (uint32_t)((ho * Wo + rwo) * CO + 4 * h) : SC_OOB / 2;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          cres[t][g] = __builtin_bit_cast(
+              uint2, __builtin_amdgcn_raw_buffer_load_b64(rres, (erow + t * 32 + 8 * g) * 2, 0, 0));
+          cra[t][g] = __builtin_amdgcn_raw_buffer_load_b32(rra, erow + t * 32 + 8 * g, 0, 0);
+        }
+    } else if (kBnBwd || a.res) {
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -218,7 +320,10 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
     }
     // the next input row into the slot this row does not read (its last reader, row ho - 1, is behind the previous
     // barrier), before the epilogue's stores
-    if (more) sc_store_row<CI>(xs + ((ho + KH) % NSLOT) * SLOT, pre);
+    if (more) store_in(xs + ((ho + KH) % NSLOT) * SLOT);
+    // kPool: element offset of this lane's window (4 channels) in the pooled output, out of range for the lanes
+    // that store none
+    const uint32_t prow = wv_ok ? (uint32_t)((ho * Wo + p / 3) * CO + 4 * h) : SC_OOB / 2;
     // epilogue: lane owns position p, channels co = t*32 + 8g + 4h + e
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -229,6 +334,37 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = acc[t][4 * g + e];
+        if constexpr (kPool) {
+          const uint2 ii = cres[t][g];
+          const float iv[4] = {hlo(ii.x), hhi(ii.x), hlo(ii.y), hhi(ii.y)};
+          const float4 bq = *reinterpret_cast<const float4*>(sbn + co);
+          const float pb[4] = {bq.x, bq.y, bq.z, bq.w};
+          float best[4];
+          uint32_t bi = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {  // the arithmetic of tail_fwd_kernel: first maximum wins, NaN propagates
+            const float s0 = hround(v[e]) + iv[e] + pb[e];
+            const float s1 = dpp_f32<0x101>(s0);   // row_shl:1, the value of lane + 1
+            const float s2 = dpp_f32<0x102>(s0);   // row_shl:2, the value of lane + 2
+            float b = s0;
+            uint32_t k = 0;
+            if (s1 > b || s1 != s1) {
+              b = s1;
+              k = 1;
+            }
+            if (s2 > b || s2 != s2) {
+              b = s2;
+              k = 2;
+            }
+            best[e] = b;
+            bi |= k << (8 * e);
+          }
+          __builtin_amdgcn_raw_buffer_store_b64(
+              __builtin_bit_cast(v2u32, make_uint2(sc_pack2(best[0], best[1]), sc_pack2(best[2], best[3]))), ry,
+              (prow + t * 32 + 8 * g) * 2, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(bi, rpa, prow + t * 32 + 8 * g, 0, 0);
+          continue;
+        }
         if constexpr (kBnBwd) {
           const uint2 cc = cres[t][g];
           const float cv[4] = {hlo(cc.x), hhi(cc.x), hlo(cc.y), hhi(cc.y)};
@@ -259,7 +395,17 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
           continue;
         }
         if (a.res) {   // the sum autograd would form: the bf16 convolution output plus the residual gradient
-          const uint2 rr = cres[t][g];
+          uint2 rr = cres[t][g];
+          if constexpr (rexp) {   // the pooled gradient at this lane's place in its window
+            rr.x = sc_exp2(rr.x, cra[t][g], (uint32_t)rj);
+            rr.y = sc_exp2(rr.y, cra[t][g] >> 16, (uint32_t)rj);
+            // every pooled element stands at exactly one column, so the sum of the expanded residual is the
+            // sum of the pooled gradient (a lane past the image loaded zeros)
+            bsum[0][t][g][0] += hlo(rr.x);
+            bsum[0][t][g][1] += hhi(rr.x);
+            bsum[0][t][g][2] += hlo(rr.y);
+            bsum[0][t][g][3] += hhi(rr.y);
+          }
           v[0] = hround(v[0]) + hlo(rr.x);
           v[1] = hround(v[1]) + hhi(rr.x);
           v[2] = hround(v[2]) + hlo(rr.y);
@@ -284,11 +430,11 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
       }
     __syncthreads();
   }
-  if constexpr (kBnBwd) {
+  if constexpr (NSUM > 0) {
     // the 32 lanes of a half-wave hold the same channels: reduce them, then the four waves through LDS (the
     // weight image is no longer needed), then one atomic per (sum, channel) per workgroup
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
+    for (int q = 0; q < NSUM; ++q)
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -300,27 +446,28 @@ __global__ __launch_bounds__(SC_T) void sconv_fwd_kernel(SConvArgs a) {
             for (int o = 1; o < 32; o <<= 1) x += __shfl_xor(x, o, 64);
             bsum[q][t][g][e] = x;
           }
-    float* red = reinterpret_cast<float*>(sc_lds);  // [4 waves][3][CO]
+    float* red = reinterpret_cast<float*>(sc_lds);  // [4 waves][NSUM][CO]
     if (r == 0) {
 #pragma unroll
-      for (int q = 0; q < 3; ++q)
+      for (int q = 0; q < NSUM; ++q)
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
           for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) red[(wv * 3 + q) * CO + t * 32 + 8 * g + 4 * h + e] = bsum[q][t][g][e];
+            for (int e = 0; e < 4; ++e) red[(wv * NSUM + q) * CO + t * 32 + 8 * g + 4 * h + e] = bsum[q][t][g][e];
     }
     __syncthreads();
-    for (int i = tid; i < 3 * CO; i += SC_T)
-      atomicAdd(&a.sums[i], (red[i] + red[3 * CO + i]) + (red[6 * CO + i] + red[9 * CO + i]));
+    for (int i = tid; i < NSUM * CO; i += SC_T)
+      atomicAdd(&a.sums[i], (red[i] + red[NSUM * CO + i]) + (red[2 * NSUM * CO + i] + red[3 * NSUM * CO + i]));
   }
 }
 
 // ---------------------------------------------------------------------------- weight gradient ------
 struct SWgradArgs {
   const hst* x;   // [N, H, W, CI]
-  const hst* dy;  // [N, Ho, W, CO]
+  const hst* dy;  // [N, Ho, W, CO]; kExp: a pooled gradient [N, Ho, W/3, CO]
+  const uint8_t* arg;        // kExp: its window index bytes [N, Ho, W/3, CO]
   float* part;               // [gridDim.x][KH*3][CO][CI]
   int N, H, W, Ho, ph;
   int64_t units;             // N * strips * nz
@@ -360,8 +507,10 @@ constexpr int SC_XR = 136;  // staged input rows per kernel row: 130 used, padde
 // through KH + 1 image slots (row (ho - ph + kh) in slot (ho + kh) % (KH + 1)) and dY rows through two, so
 // each input row is read from HBM once per unit and one barrier per row separates the writes of row ho from
 // the MFMA reads of row ho - 1 (they never touch the same slot).
-template <int CI, int CO, int KH>
-__global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
+// kExp: dY is a pooled gradient (a.dy, a.arg): the raw pooled items are loaded and expanded to full width when they
+// are written to LDS.
+template <int CI, int CO, int KH, bool kExp = false>
+__device__ __forceinline__ void sconv_wgrad_body(SWgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char sc_lds[];
   constexpr int NSLOT = KH + 1, XSLOT = SC_XR * CI * 2, DSLOT = SC_P * CO * 2;
   char* dyi = sc_lds;                       // 2 x [SC_P][CO]
@@ -396,21 +545,37 @@ __global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
       if (i < XV) *reinterpret_cast<uint4*>(slot + sc_img<CI>(i / (CI / 8), i % (CI / 8))) = r[j];
     }
   };
+  uint2 ra[kExp ? DN : 1];   // kExp: the index bytes of the dY items in flight
   auto load_dy = [&](uint4 (&r)[DN], int n, int ho, int p0) {
 #pragma unroll
     for (int j = 0; j < DN; ++j) {
       const int i = tid + SC_T * j;
       const int ch = i % (CO / 8), pp = i / (CO / 8), wi = p0 + pp;
       r[j] = make_uint4(0, 0, 0, 0);
+      if constexpr (kExp) {
+        const int Wo = a.W / 3, wo = wi / 3;
+        ra[j] = make_uint2(0, 0);
+        if (i < DV && ho < a.Ho && wo < Wo) {
+          const int64_t e = (((int64_t)n * a.Ho + ho) * Wo + wo) * CO + ch * 8;
+          r[j] = *reinterpret_cast<const uint4*>(a.dy + e);
+          ra[j] = *reinterpret_cast<const uint2*>(a.arg + e);
+        }
+        continue;
+      }
       if (i < DV && ho < a.Ho && wi < a.W)
         r[j] = *reinterpret_cast<const uint4*>(a.dy + (((int64_t)n * a.Ho + ho) * a.W + wi) * CO + ch * 8);
     }
   };
-  auto store_dy = [&](char* slot, const uint4 (&r)[DN]) {
+  auto store_dy = [&](char* slot, const uint4 (&r)[DN], int p0) {
 #pragma unroll
     for (int j = 0; j < DN; ++j) {
       const int i = tid + SC_T * j;
-      if (i < DV) *reinterpret_cast<uint4*>(slot + sc_img<CO>(i / (CO / 8), i % (CO / 8))) = r[j];
+      if constexpr (!kExp) {
+        if (i < DV) *reinterpret_cast<uint4*>(slot + sc_img<CO>(i / (CO / 8), i % (CO / 8))) = r[j];
+      } else {
+        const uint4 v = sc_expand(r[j], ra[j], (uint32_t)((p0 + i / (CO / 8)) % 3));
+        if (i < DV) *reinterpret_cast<uint4*>(slot + sc_img<CO>(i / (CO / 8), i % (CO / 8))) = v;
+      }
     }
   };
   uint4 rx[XN], rd[DN];
@@ -426,7 +591,7 @@ __global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
       store_x(xi + ((ho0 + kh) % NSLOT) * XSLOT, rx);
     }
     load_dy(rd, n, ho0, p0);
-    store_dy(dyi + (ho0 & 1) * DSLOT, rd);
+    store_dy(dyi + (ho0 & 1) * DSLOT, rd, p0);
     if (ho0 + 1 < ho1) {  // prefetch the rows output row ho0 + 1 adds
       load_x(rx, n, ho0 + 1 - a.ph + KH - 1, p0);
       load_dy(rd, n, ho0 + 1, p0);
@@ -451,7 +616,7 @@ __global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
       if (ho + 1 < ho1) {
         // the slots of rows ho - 1 (X) and ho - 1 (dY) are free: every wave passed this row's barrier
         store_x(xi + ((ho + KH) % NSLOT) * XSLOT, rx);
-        store_dy(dyi + ((ho + 1) & 1) * DSLOT, rd);
+        store_dy(dyi + ((ho + 1) & 1) * DSLOT, rd, p0);
         if (ho + 2 < ho1) {
           load_x(rx, n, ho + 2 - a.ph + KH - 1, p0);
           load_dy(rd, n, ho + 2, p0);
@@ -474,6 +639,17 @@ __global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
       out[((int64_t)tap * CO + co) * CI + ci] = acc[j][i];
     }
   }
+}
+
+template <int CI, int CO, int KH>
+__global__ __launch_bounds__(SC_T) void sconv_wgrad_kernel(SWgradArgs a) {
+  sconv_wgrad_body<CI, CO, KH, false>(a);
+}
+// The pooled-gradient variant keeps the plain kernel's workgroups per CU (the LDS image allows 3 at 32 channels:
+// 3 waves per SIMD), which its extra index registers would otherwise lose.
+template <int CI, int CO, int KH>
+__global__ __launch_bounds__(SC_T, CI == 32 && CO == 32 ? 3 : 1) void sconv_wgrad_pool_kernel(SWgradArgs a) {
+  sconv_wgrad_body<CI, CO, KH, true>(a);
 }
 
 // Fixed-order reduction of the per-workgroup partials [nblk][n]: stage 1 sums slice z of SC_RS slices of the
@@ -501,13 +677,16 @@ __global__ void sconv_wgrad_reduce2_kernel(const float* __restrict__ part2, int6
   dw[i] = s;
 }
 
-template <int CI, int CO, int KH, bool kBnBwd = false>
+template <int CI, int CO, int KH, bool kBnBwd = false, bool kPool = false, bool kExpIn = false, bool kExpRes = false>
 static int sconv_fwd_launch(const SConvArgs& a, hipStream_t st) {
   // the kernel's per-utterance buffer ranges and 32-bit offsets (the sentinel SC_OOB must lie past every range)
   if ((int64_t)a.H * a.W * CI * 2 >= (int64_t)SC_OOB - 4096 || (int64_t)a.Ho * a.W * CO * 2 >= (int64_t)SC_OOB - 4096)
     return RDX_EUNSUPPORTED;
-  const size_t smem = (size_t)(KH + 1) * SC_PW * CI * 2 + (size_t)KH * 3 * CO * CI * 2 + 5 * CO * sizeof(float);
-  const int strips = (a.W + SC_P - 1) / SC_P;
+  if ((kPool || kExpIn || kExpRes) && a.W < 3) return RDX_EUNSUPPORTED;   // no pooled column at all
+  const size_t smem = (size_t)(KH + 1) * (kPool ? SC_PPW : SC_PW) * CI * 2 + (size_t)KH * 3 * CO * CI * 2 +
+                      5 * CO * sizeof(float);
+  // kPool: strips of SC_PP positions over the 3 (W / 3) columns that have a pool window
+  const int strips = kPool ? (a.W / 3 * 3 + SC_PP - 1) / SC_PP : (a.W + SC_P - 1) / SC_P;
   // one round of resident workgroups (256 CUs x the workgroups the LDS image allows per CU: 4 at 32 x 32
   // channels, 1 at 64 x 64): split the rows when strips x N alone is fewer (each split restages the weights
   // and KH - 1 halo rows), never more (a second round would restage for nothing)
@@ -528,15 +707,18 @@ static int sconv_fwd_launch(const SConvArgs& a, hipStream_t st) {
   SConvArgs b = a;
   b.rows_per = (a.Ho + nz - 1) / nz;
   dim3 grid((unsigned)strips, (unsigned)a.N, (unsigned)((a.Ho + b.rows_per - 1) / b.rows_per));
-  hipLaunchKernelGGL((sconv_fwd_kernel<CI, CO, KH, kBnBwd>), grid, dim3(SC_T), smem, st, b);
+  hipLaunchKernelGGL((sconv_fwd_kernel<CI, CO, KH, kBnBwd, kPool, kExpIn, kExpRes>), grid, dim3(SC_T), smem, st, b);
   RDX_LAUNCH_CHECK();
   return RDX_OK;
 }
 
-template <int CI, int CO, int KH>
+template <int CI, int CO, int KH, bool kExp = false>
 static int sconv_wgrad_launch(const SWgradArgs& a, int nblk, hipStream_t st) {
   const size_t smem = (2 * (size_t)SC_P * CO + (size_t)(KH + 1) * SC_XR * CI) * 2;
-  hipLaunchKernelGGL((sconv_wgrad_kernel<CI, CO, KH>), dim3((unsigned)nblk), dim3(SC_T), smem, st, a);
+  if constexpr (kExp)
+    hipLaunchKernelGGL((sconv_wgrad_pool_kernel<CI, CO, KH>), dim3((unsigned)nblk), dim3(SC_T), smem, st, a);
+  else
+    hipLaunchKernelGGL((sconv_wgrad_kernel<CI, CO, KH>), dim3((unsigned)nblk), dim3(SC_T), smem, st, a);
   RDX_LAUNCH_CHECK();
   return RDX_OK;
 }
@@ -573,6 +755,8 @@ extern "C" int rdx_sconv_fwd(const void* x, const void* w, void* y, void* y2, co
   a.c = nullptr;
   a.sums = nullptr;
   a.res = nullptr;
+  a.xarg = a.rarg = nullptr;
+  a.parg = nullptr;
   a.N = N;
   a.H = H;
   a.W = W;
@@ -600,6 +784,8 @@ extern "C" int rdx_sconv_fwd_res(const void* x, const void* w, void* y, const vo
   a.c = nullptr;
   a.sums = nullptr;
   a.res = (const hst*)res;
+  a.xarg = a.rarg = nullptr;
+  a.parg = nullptr;
   a.N = N;
   a.H = H;
   a.W = W;
@@ -630,6 +816,8 @@ extern "C" int rdx_sconv_dgrad_bnselu(const void* dy, const void* w, const void*
   a.c = (const hst*)c;
   a.sums = sums;
   a.res = nullptr;
+  a.xarg = a.rarg = nullptr;
+  a.parg = nullptr;
   a.N = N;
   a.H = H;
   a.W = W;
@@ -638,6 +826,99 @@ extern "C" int rdx_sconv_dgrad_bnselu(const void* dy, const void* w, const void*
   RDX_REQUIRE(a.Ho > 0);
   if (ci == 64) return sconv_fwd_launch<64, 64, 2, true>(a, as_stream(stream));
   return sconv_fwd_launch<32, 32, 2, true>(a, as_stream(stream));
+}
+
+// A residual block's conv2 and tail in one pass: y[N, H-1, W/3, c] = MaxPool2d((1, 3))(bf16(conv2(x)) + idn + bias)
+// and arg, its window index bytes — rdx_sconv_fwd (kh 2, ph 0) followed by rdx_res_tail_fwd, bit for bit, without
+// the full-width convolution output. x [N, H, W, c], idn [N, H-1, W, c], c = ci = co in {32, 64}, W >= 3.
+extern "C" int rdx_sconv_fwd_pool(const void* x, const void* w, const void* idn, const float* bias, void* y,
+                                  uint8_t* arg, int N, int H, int W, int ci, int co, void* stream) {
+  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  RDX_REQUIRE(x && w && idn && bias && y && arg && N > 0 && H > 1 && W > 0 && N <= 65535);
+  RDX_REQUIRE(al(x) && al(w) && al(idn) && al(y) && al(arg));
+  if (!((ci == 32 && co == 32) || (ci == 64 && co == 64)) || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a;
+  a.x = (const hst*)x;
+  a.w = (const hst*)w;
+  a.y = (hst*)y;
+  a.y2 = nullptr;
+  a.bn = bias;
+  a.c = nullptr;
+  a.sums = nullptr;
+  a.res = (const hst*)idn;
+  a.xarg = a.rarg = nullptr;
+  a.parg = arg;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.ph = 0;
+  a.Ho = H - 1;
+  if (ci == 64) return sconv_fwd_launch<64, 64, 2, false, true>(a, as_stream(stream));
+  return sconv_fwd_launch<32, 32, 2, false, true>(a, as_stream(stream));
+}
+
+// rdx_sconv_fwd_res with the residual given as a pooled gradient: res = the scatter of (dp, arg) [N, Ho, W/3, co]
+// to full width (rdx_res_tail_bwd's dx), formed in the epilogue instead of being read; dbias [co] += the
+// per-channel sum of dp (rdx_res_tail_bwd's bias gradient; fp32 atomics, zeroed by the caller).
+extern "C" int rdx_sconv_fwd_res_pool(const void* x, const void* w, void* y, const void* dp, const uint8_t* arg,
+                                      float* dbias, int N, int H, int W, int ci, int co, int kh, int ph, void* stream) {
+  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  RDX_REQUIRE(x && w && y && dp && arg && dbias && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
+  RDX_REQUIRE(al(x) && al(w) && al(y) && al(dp) && al(arg));
+  SConvArgs a;
+  a.x = (const hst*)x;
+  a.w = (const hst*)w;
+  a.y = (hst*)y;
+  a.y2 = nullptr;
+  a.bn = nullptr;
+  a.c = nullptr;
+  a.sums = dbias;
+  a.res = (const hst*)dp;
+  a.xarg = nullptr;
+  a.rarg = arg;
+  a.parg = nullptr;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.ph = ph;
+  a.Ho = H + 2 * ph - kh + 1;
+  RDX_REQUIRE(a.Ho > 0 && N <= 65535);
+  // conv1's input gradient in the blocks without downsampling: 2 x 3, equal channel counts
+  if (kh != 2 || ci != co) return RDX_EUNSUPPORTED;
+  if (ci == 64) return sconv_fwd_launch<64, 64, 2, false, false, false, true>(a, as_stream(stream));
+  if (ci == 32) return sconv_fwd_launch<32, 32, 2, false, false, false, true>(a, as_stream(stream));
+  return RDX_EUNSUPPORTED;
+}
+
+// rdx_sconv_dgrad_bnselu with conv2's output gradient given as a pooled gradient (dp, arg) [N, H, W/3, ci]: each
+// input row is expanded to full width while it is staged.
+extern "C" int rdx_sconv_dgrad_bnselu_pool(const void* dp, const uint8_t* arg, const void* w, const void* c, void* dc,
+                                           const float* bn, float* sums, int N, int H, int W, int ci, int co, int kh,
+                                           int ph, void* stream) {
+  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  RDX_REQUIRE(dp && arg && w && c && dc && bn && sums && N > 0 && H > 0 && W > 0 && ph >= 0 && ph <= kh);
+  RDX_REQUIRE(al(dp) && al(arg) && al(w) && al(c) && al(dc) && N <= 65535);
+  if (!((ci == 32 && co == 32) || (ci == 64 && co == 64)) || kh != 2 || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a;
+  a.x = (const hst*)dp;
+  a.w = (const hst*)w;
+  a.y = (hst*)dc;
+  a.y2 = nullptr;
+  a.bn = bn;
+  a.c = (const hst*)c;
+  a.sums = sums;
+  a.res = nullptr;
+  a.xarg = arg;
+  a.rarg = nullptr;
+  a.parg = nullptr;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.ph = ph;
+  a.Ho = H + 2 * ph - kh + 1;
+  RDX_REQUIRE(a.Ho > 0);
+  if (ci == 64) return sconv_fwd_launch<64, 64, 2, true, false, true>(a, as_stream(stream));
+  return sconv_fwd_launch<32, 32, 2, true, false, true>(a, as_stream(stream));
 }
 
 // Both 16-bit operand layouts of up to SC_WP_MAX convolution weights [co][ci][kh][3] (fp32) in one launch: wf
@@ -705,16 +986,50 @@ static int sc_wgrad_blocks(int N, int Ho, int W) {
 // rows of kh*3*co*ci fp32 the weight-gradient scratch needs: one partial per workgroup + the reduction slices
 extern "C" int rdx_sconv_wgrad_nblk(int N, int Ho, int W) { return sc_wgrad_blocks(N, Ho, W) + SC_RS; }
 
+// The input gradient of block 2's conv_downsample (1 x 3, 32 -> 64 channels) from the pooled gradient (dp, arg)
+// [N, H, W/3, 64] of its output: rdx_sconv_fwd of rdx_res_tail_bwd's scatter with the flipped kernel w [3][32][64],
+// expanded while it is staged. ci = 64 (the gradient's channels), co = 32, kh = 1, ph = 0; dx [N, H, W, 32].
+extern "C" int rdx_sconv_dgrad_pool(const void* dp, const uint8_t* arg, const void* w, void* dx, int N, int H, int W,
+                                    int ci, int co, int kh, int ph, void* stream) {
+  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  RDX_REQUIRE(dp && arg && w && dx && N > 0 && H > 0 && W > 0 && N <= 65535);
+  RDX_REQUIRE(al(dp) && al(arg) && al(w) && al(dx));
+  if (ci != 64 || co != 32 || kh != 1 || ph != 0 || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a;
+  a.x = (const hst*)dp;
+  a.w = (const hst*)w;
+  a.y = (hst*)dx;
+  a.y2 = nullptr;
+  a.bn = nullptr;
+  a.c = nullptr;
+  a.sums = nullptr;
+  a.res = nullptr;
+  a.xarg = arg;
+  a.rarg = nullptr;
+  a.parg = nullptr;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.ph = 0;
+  a.Ho = H;
+  return sconv_fwd_launch<64, 32, 1, false, false, true>(a, as_stream(stream));
+}
+
 // dw [kh*3][co][ci] fp32 = sum over positions of dy (x) shifted x; part: [nblk][kh*3*co*ci] fp32 scratch,
 // nblk = rdx_sconv_wgrad_nblk(N, Ho, W).
-extern "C" int rdx_sconv_wgrad(const void* x, const void* dy, float* dw, float* part, int N, int H, int W, int ci,
-                               int co, int kh, int ph, void* stream) {
+// arg != NULL: dy is a pooled gradient (dy, arg) [N, Ho, W/3, co]
+static int sc_wgrad_run(const void* x, const void* dy, const uint8_t* arg, float* dw, float* part, int N,
+                        int H, int W, int ci, int co, int kh, int ph, void* stream) {
   auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   RDX_REQUIRE(x && dy && dw && part && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(x) && al(dy));
+  RDX_REQUIRE(al(x) && al(dy) && (!arg || al(arg)));
+  // pooled gradients: conv2 (2 x 3, equal channels) and block 2's conv_downsample (1 x 3, 32 -> 64)
+  if (arg && (W < 3 || !((ci == co && kh == 2 && (ci == 32 || ci == 64)) || (ci == 32 && co == 64 && kh == 1))))
+    return RDX_EUNSUPPORTED;
   SWgradArgs a;
   a.x = (const hst*)x;
   a.dy = (const hst*)dy;
+  a.arg = arg;
   a.part = part;
   a.N = N;
   a.H = H;
@@ -735,7 +1050,10 @@ extern "C" int rdx_sconv_wgrad(const void* x, const void* dy, float* dw, float* 
   const int nblk = cap < 256 * per_cu ? cap : 256 * per_cu;
   hipStream_t st = as_stream(stream);
   int rc = RDX_EUNSUPPORTED;
-  if (ci == 32 && co == 32 && kh == 2) rc = sconv_wgrad_launch<32, 32, 2>(a, nblk, st);
+  if (arg && kh == 1) rc = sconv_wgrad_launch<32, 64, 1, true>(a, nblk, st);
+  else if (arg && ci == 32) rc = sconv_wgrad_launch<32, 32, 2, true>(a, nblk, st);
+  else if (arg) rc = sconv_wgrad_launch<64, 64, 2, true>(a, nblk, st);
+  else if (ci == 32 && co == 32 && kh == 2) rc = sconv_wgrad_launch<32, 32, 2>(a, nblk, st);
   else if (ci == 32 && co == 64 && kh == 2) rc = sconv_wgrad_launch<32, 64, 2>(a, nblk, st);
   else if (ci == 64 && co == 32 && kh == 2) rc = sconv_wgrad_launch<64, 32, 2>(a, nblk, st);
   else if (ci == 64 && co == 64 && kh == 2) rc = sconv_wgrad_launch<64, 64, 2>(a, nblk, st);
@@ -751,4 +1069,18 @@ extern "C" int rdx_sconv_wgrad(const void* x, const void* dy, float* dw, float* 
   hipLaunchKernelGGL(sconv_wgrad_reduce2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part2, n, dw);
   RDX_LAUNCH_CHECK();
   return RDX_OK;
+}
+
+extern "C" int rdx_sconv_wgrad(const void* x, const void* dy, float* dw, float* part, int N, int H, int W, int ci,
+                               int co, int kh, int ph, void* stream) {
+  return sc_wgrad_run(x, dy, nullptr, dw, part, N, H, W, ci, co, kh, ph, stream);
+}
+
+// rdx_sconv_wgrad of conv2 (kh 2, ci = co in {32, 64}) or of block 2's conv_downsample (kh 1, 32 -> 64) with dy
+// given as a pooled gradient (dp, arg)
+// [N, Ho, W/3, co], expanded while it is staged.
+extern "C" int rdx_sconv_wgrad_pool(const void* x, const void* dp, const uint8_t* arg, float* dw, float* part, int N,
+                                    int H, int W, int ci, int co, int kh, int ph, void* stream) {
+  RDX_REQUIRE(arg);
+  return sc_wgrad_run(x, dp, arg, dw, part, N, H, W, ci, co, kh, ph, stream);
 }

@@ -149,6 +149,11 @@ SIGNATURES = {
                                        c_int, c_vp]),
     "rdx_sconv_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "rdx_sconv_fwd_res": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "rdx_sconv_fwd_pool": (c_int, [c_vp] * 6 + [c_int] * 5 + [c_vp]),
+    "rdx_sconv_fwd_res_pool": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_vp]),
+    "rdx_sconv_dgrad_bnselu_pool": (c_int, [c_vp] * 7 + [c_int] * 7 + [c_vp]),
+    "rdx_sconv_dgrad_pool": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
+    "rdx_sconv_wgrad_pool": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp]),
     "rdx_sconv_wgrad_nblk": (c_int, [c_int, c_int, c_int]),
     "rdx_sconv_wgrad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "rdx_sconv_wprep_many": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

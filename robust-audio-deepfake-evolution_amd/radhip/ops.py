@@ -877,6 +877,81 @@ def _sconv_run(x, w_tap, ci, co, kh, ph, y2=None, bn=None, res=None):
     return y
 
 
+SCONV_POOL_DEFAULT = "1"
+
+
+def sconv_pool_ok(w2_shape, W, half):
+    """conv2 shapes whose residual tail runs without the full-width tensors (half "fwd": rdx_sconv_fwd_pool; "bwd":
+    the pooled-gradient backward kernels): 2 x 3, C_in = C_out in {32, 64}, at least one pool window.
+    RADHIP_SCONV_POOL=1 both halves, fwd / bwd that half only, 0 none (the convolution, then rdx_res_tail_fwd /
+    rdx_res_tail_bwd around the full-width tensors)."""
+    co, ci, kh, kw = w2_shape
+    return (ci == co and ci in SCONV_CH and kh == 2 and kw == 3 and W >= 3
+            and os.environ.get("RADHIP_SCONV_POOL", SCONV_POOL_DEFAULT) in ("1", half))
+
+
+def _sconv_run_pool(x, w_tap, idn, bias, c):
+    """MaxPool2d((1, 3))(conv2(x) + idn + bias) and its window index bytes in one launch (kernel 2 x 3, no row padding,
+    c -> c channels); x, idn: 16-bit NHWC, bias fp32 [c]."""
+    N, _, H, W = x.shape
+    Ho = H - 1
+    if idn.shape != (N, c, Ho, W) or idn.dtype != x.dtype or not idn.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("radhip sconv: identity must be NHWC of the convolution output's shape and dtype")
+    y = torch.empty(N, c, Ho, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    arg = torch.empty(N, c, Ho, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
+    # x and the identity in, a third of a full-width output (+ one index byte per element) out
+    nbytes = 2.0 * (N * H * W * c + N * Ho * W * c) + 3.0 * y.numel()
+    with _timed("sconv_fwd", x, nbytes, shape=(N, H, W, c, c, 2, 0)):
+        check(_L(x).rdx_sconv_fwd_pool(_p(x), _p(w_tap), _p(idn), _p(bias), _p(y), _p(arg), N, H, W, c, c, _stream(x)),
+              "sconv_fwd_pool")
+    return y, arg
+
+
+def _sconv_run_res_pool(x, w_tap, dp, arg, dbias, ci, co, kh, ph):
+    """_sconv_run with the residual given as the pooled gradient (dp, arg) of width W // 3; dbias [co] fp32 (zeroed)
+    receives dp's per-channel sum."""
+    N, _, H, W = x.shape
+    Ho = H + 2 * ph - kh + 1
+    y = torch.empty(N, co, Ho, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    nbytes = 2.0 * (N * H * W * ci + N * Ho * W * co) + 3.0 * dp.numel()
+    with _timed("sconv_fwd", x, nbytes, shape=(N, H, W, ci, co, kh, ph)):
+        check(_L(x).rdx_sconv_fwd_res_pool(_p(x), _p(w_tap), _p(y), _p(dp), _p(arg), _p(dbias), N, H, W, ci, co, kh, ph,
+                                           _stream(x)), "sconv_fwd_res_pool")
+    return y
+
+
+def _sconv_wgrad_pool(x, dp, arg, weight_shape):
+    """The weight gradient of conv2 or of block 2's conv_downsample (no row padding) from the pooled gradient (dp, arg)
+    of its output."""
+    co, ci, kh, kw = weight_shape
+    N, _, H, W = x.shape
+    Ho = dp.shape[2]
+    nblk = lib().rdx_sconv_wgrad_nblk(N, Ho, W)
+    part = torch.empty(nblk, kh * 3 * co * ci, device=x.device, dtype=torch.float32)
+    dw = torch.empty(kh * 3, co, ci, device=x.device, dtype=torch.float32)
+    with _timed("sconv_wgrad", x, 2.0 * N * H * W * ci + 3.0 * dp.numel(), shape=(N, H, W, ci, co, kh, 0)):
+        check(_L(x).rdx_sconv_wgrad_pool(_p(x), _p(dp), _p(arg), _p(dw), _p(part), N, H, W, ci, co, kh, 0, _stream(x)),
+              "sconv_wgrad_pool")
+    return dw.view(kh, 3, co, ci).permute(2, 3, 0, 1)
+
+
+def _sconv_dgrad_pool(dp, arg, wd, weight_shape, W):
+    """The input gradient [N, ci, H, W] of block 2's conv_downsample (weight_shape (64, 32, 1, 3), no row padding) from the
+    pooled gradient (dp, arg) [N, 64, H, W // 3] of its output; wd: the flipped kernel [3][ci][co]."""
+    co, ci, kh, kw = weight_shape
+    N, _, H, _ = dp.shape
+    dx = torch.empty(N, ci, H, W, device=dp.device, dtype=dp.dtype, memory_format=torch.channels_last)
+    with _timed("sconv_fwd", dp, 3.0 * dp.numel() + 2.0 * dx.numel(), shape=(N, H, W, co, ci, kh, 0)):
+        check(_L(dp).rdx_sconv_dgrad_pool(_p(dp), _p(arg), _p(wd), _p(dx), N, H, W, co, ci, kh, 0, _stream(dp)),
+              "sconv_dgrad_pool")
+    return dx
+
+
+def _pooled_grad_ok(dy, arg):
+    """A pool gradient the pooled-gradient kernels take as it is: the argmax tensor's shape, 16-byte aligned."""
+    return dy.shape == arg.shape and dy.data_ptr() % 16 == 0
+
+
 def _sconv_backward(x, dy, wd, weight_shape, ph, need_dx):
     co, ci, kh, kw = weight_shape
     N, _, H, W = x.shape
@@ -949,16 +1024,30 @@ class SConvBnSelu(torch.autograd.Function):
         return dx, dw.to(wdt), None, sums[0], None, None, sums[1], sums[2]
 
 
-def _conv2_grad_to_c(da, out1, c, wd2, w2_shape, bn5, f32):
+def _fused_dgrad_bn_ok(w2_shape):
+    co2, ci2, kh2, _ = w2_shape
+    return ci2 == co2 and ci2 in (32, 64) and kh2 == 2 and os.environ.get("RADHIP_FUSED_DGRAD_BN", "1") != "0"
+
+
+def _conv2_grad_to_c(da, out1, c, wd2, w2_shape, bn5, f32, arg=None):
     """From conv2's output gradient da back to conv1's pre-activation c: dc (bf16, c's shape), the frozen
     BN / conv1-bias sums [3][C] (d conv_bias, d gamma, d beta) and dw2. The 32- and 64-channel blocks run conv2's
     input gradient and the BN + SELU backward as ONE kernel (rdx_sconv_dgrad_bnselu: dO1 stays on chip);
-    otherwise the input gradient and rdx_bnselu_bwd run one after the other."""
+    otherwise the input gradient and rdx_bnselu_bwd run one after the other. With arg, (da, arg) is the pooled
+    gradient of the block's max-pool (width W // 3: sconv_pool_ok and _fused_dgrad_bn_ok shapes only) and both
+    kernels expand it while they stage it."""
     co2, ci2, kh2, _ = w2_shape
     N, C, Ho, W = c.shape
     dc = torch.empty_like(c)
     sums = torch.zeros(3, C, device=c.device, dtype=torch.float32)
-    if ci2 == co2 and ci2 in (32, 64) and kh2 == 2 and os.environ.get("RADHIP_FUSED_DGRAD_BN", "1") != "0":
+    if arg is not None:
+        H = da.shape[2]
+        nbytes = 3.0 * da.numel() + 2.0 * (2 * N * Ho * W * C)
+        with _timed("sconv_dgrad_bnselu", da, nbytes, shape=(N, H, W)):
+            check(_L(da).rdx_sconv_dgrad_bnselu_pool(_p(da), _p(arg), _p(wd2), _p(c), _p(dc), _p(bn5), _p(sums), N, H, W,
+                                                    co2, ci2, kh2, kh2 - 1, _stream(da)), "sconv_dgrad_bnselu_pool")
+        return dc, sums, _sconv_wgrad_pool(out1, da, arg, w2_shape)
+    if _fused_dgrad_bn_ok(w2_shape):
         H = da.shape[2]
         nbytes = 2.0 * (N * H * W * co2 + 2 * N * Ho * W * C)
         with _timed("sconv_dgrad_bnselu", da, nbytes, shape=(N, H, W)):
@@ -1030,7 +1119,9 @@ class ResBlockIdentity(torch.autograd.Function):
     as one autograd op. Forward: SConvBnSeluSConv's and ResTail's kernels. Backward: ResTail's scatter, conv2's input
     gradient with the BN + SELU backward, then the block input's gradient in ONE pass, conv1's input gradient with
     the identity branch's gradient added in its epilogue (rdx_sconv_fwd_res): the bits autograd's separate add of
-    the two full-size gradients produces, without that read-read-write pass."""
+    the two full-size gradients produces, without that read-read-write pass. Where sconv_pool_ok, conv2's launch does
+    the residual sum and the pool in its epilogue (no full-width conv2 output, no ResTail launch) and the backward
+    kernels take the pool's gradient as (dy, argmax byte) instead of ResTail's full-width scatter: the same bits."""
 
     @staticmethod
     def forward(ctx, x, w1, conv_bias, mean, invstd, gamma, beta, w2, b2):
@@ -1045,14 +1136,18 @@ class ResBlockIdentity(torch.autograd.Function):
         out1 = torch.empty(N, co, H + 1, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
         c = _sconv_run(x, wf1, ci, co, kh, 1, y2=out1, bn=bn5[:4])
         co2, ci2, kh2, _ = w2.shape
-        a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
-        if a.shape != x.shape:
-            raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(x.shape)}")
-        y = torch.empty(N, co2, H, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-        arg = torch.empty(N, co2, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
         bf = b2.detach().contiguous().float()
-        check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(x), _p(bf), _p(y), _p(arg), N * H, W, co2, _stream(a)),
-              "res_tail_fwd")
+        if sconv_pool_ok(w2.shape, W, "fwd") and (N, co2, H + 2 - kh2, W) == tuple(x.shape):
+            # conv2 with the residual sum and the max-pool in its epilogue: its full-width output is never stored
+            y, arg = _sconv_run_pool(out1, wf2, x, bf, co2)
+        else:
+            a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
+            if a.shape != x.shape:
+                raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(x.shape)}")
+            y = torch.empty(N, co2, H, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+            arg = torch.empty(N, co2, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
+            check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(x), _p(bf), _p(y), _p(arg), N * H, W, co2,
+                                         _stream(a)), "res_tail_fwd")
         ctx.save_for_backward(x, wd1, c, out1, wd2, bn5, arg, *f32)
         ctx.meta = (tuple(w1.shape), w1.dtype, tuple(w2.shape), w2.dtype, x_dtype)
         return y
@@ -1063,16 +1158,92 @@ class ResBlockIdentity(torch.autograd.Function):
         s1, w1dt, s2, w2dt, x_dtype = ctx.meta
         N, C, H, W = x.shape
         dy = _nhwc(dy.to(x.dtype))
-        ds = torch.empty(N, C, H, W, device=dy.device, dtype=x.dtype, memory_format=torch.channels_last)
         dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
-        check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C, _stream(dy)),
-              "res_tail_bwd")
-        dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
         co, ci, kh, _ = s1
-        dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=ds) if ctx.needs_input_grad[0] else None
+        if (sconv_pool_ok(s2, W, "bwd") and _fused_dgrad_bn_ok(s2) and ctx.needs_input_grad[0] and co == ci and kh == 2
+                and _pooled_grad_ok(dy, arg)):
+            # the pool gradient stays pooled: its three consumers expand (dy, arg) while they stage it, and the
+            # bias gradient (the sum of dy) comes out of the block input gradient's epilogue
+            dc, sums, dw2 = _conv2_grad_to_c(dy, out1, c, wd2, s2, bn5, f32, arg=arg)
+            dx = _sconv_run_res_pool(dc, wd1, dy, arg, dbias, co, ci, kh, kh - 1 - 1)
+        else:
+            ds = torch.empty(N, C, H, W, device=dy.device, dtype=x.dtype, memory_format=torch.channels_last)
+            check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C,
+                                          _stream(dy)), "res_tail_bwd")
+            dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
+            dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=ds) if ctx.needs_input_grad[0] else None
         _, dw1 = _sconv_backward(x, dc, wd1, s1, 1, False)
         return (dx.to(x_dtype) if dx is not None else None, dw1.to(w1dt), sums[0], None, None, sums[1], sums[2],
                 dw2.to(w2dt), dbias)
+
+
+class ResBlockDown(torch.autograd.Function):
+    """The downsampling residual block with 32 -> 64 channels (SincNet block 2: Residual_block.forward,
+    src/models/DualStreamSEMamba.py:182-200, frozen BN):
+    MaxPool2d((1, 3))(conv2(selu(bn2(conv1(x) + cb))) + conv_downsample(x) + b2 + bd) as one autograd op, so that the
+    max-pool runs without its full-width tensors as in ResBlockIdentity. Forward: conv1 with the BN + SELU epilogue,
+    conv_downsample, then conv2 with the residual sum and the pool in its epilogue (sconv_pool_ok "fwd"; otherwise
+    conv2 and rdx_res_tail_fwd). Backward: the pool gradient stays (dy, argmax byte) for conv2's input and weight
+    gradients and conv_downsample's (sconv_pool_ok "bwd"; otherwise rdx_res_tail_bwd's full-width scatter feeds the
+    plain kernels); the block input's gradient is conv1's input gradient with conv_downsample's added in its
+    epilogue (rdx_sconv_fwd_res), the bits autograd's add of the two produces. The same bits as SConvBnSeluSConv +
+    SConv + ResTail; the two biases' gradient (the sum of dy) is a reduction over the pooled tensor."""
+
+    @staticmethod
+    def forward(ctx, x, w1, conv_bias, mean, invstd, gamma, beta, w2, wdn, bias):
+        _require_gpu(x)
+        x_dtype = x.dtype
+        x = _nhwc(x.to(half_dtype()))
+        co, ci, kh, _ = w1.shape
+        wf1, wd1 = _sconv_w(w1, x.dtype)
+        wf2, wd2 = _sconv_w(w2, x.dtype)
+        wfd, wdd = _sconv_w(wdn, x.dtype)
+        f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
+        N, _, H, W = x.shape
+        out1 = torch.empty(N, co, H + 1, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+        c = _sconv_run(x, wf1, ci, co, kh, 1, y2=out1, bn=bn5[:4])
+        co2, ci2, kh2, _ = w2.shape
+        idn = _sconv_run(x, wfd, ci, wdn.shape[0], wdn.shape[2], 0)
+        bf = bias.detach().contiguous().float()
+        if sconv_pool_ok(w2.shape, W, "fwd") and (N, co2, H + 2 - kh2, W) == tuple(idn.shape):
+            y, arg = _sconv_run_pool(out1, wf2, idn, bf, co2)
+        else:
+            a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
+            if a.shape != idn.shape:
+                raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(idn.shape)}")
+            y = torch.empty(N, co2, H, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+            arg = torch.empty(N, co2, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
+            check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(idn), _p(bf), _p(y), _p(arg), N * H, W, co2,
+                                         _stream(a)), "res_tail_fwd")
+        ctx.save_for_backward(x, wd1, c, out1, wd2, wdd, bn5, arg, *f32)
+        ctx.meta = (tuple(w1.shape), w1.dtype, tuple(w2.shape), w2.dtype, tuple(wdn.shape), wdn.dtype, x_dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wd1, c, out1, wd2, wdd, bn5, arg, *f32 = ctx.saved_tensors
+        s1, w1dt, s2, w2dt, sd, wddt, x_dtype = ctx.meta
+        N, _, H, W = x.shape
+        C = s2[0]
+        dy = _nhwc(dy.to(x.dtype))
+        co, ci, kh, _ = s1
+        if (sconv_pool_ok(s2, W, "bwd") and _fused_dgrad_bn_ok(s2) and tuple(sd) == (64, 32, 1, 3)
+                and _pooled_grad_ok(dy, arg)):
+            dbias = dy.sum((0, 2, 3), dtype=torch.float32)
+            dc, sums, dw2 = _conv2_grad_to_c(dy, out1, c, wd2, s2, bn5, f32, arg=arg)
+            dxd = _sconv_dgrad_pool(dy, arg, wdd, sd, W) if ctx.needs_input_grad[0] else None
+            dwd = _sconv_wgrad_pool(x, dy, arg, sd)
+        else:
+            ds = torch.empty(N, C, H, W, device=dy.device, dtype=x.dtype, memory_format=torch.channels_last)
+            dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
+            check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C,
+                                          _stream(dy)), "res_tail_bwd")
+            dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
+            dxd, dwd = _sconv_backward(x, ds, wdd, sd, 0, ctx.needs_input_grad[0])
+        dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=dxd) if ctx.needs_input_grad[0] else None
+        _, dw1 = _sconv_backward(x, dc, wd1, s1, 1, False)
+        return (dx.to(x_dtype) if dx is not None else None, dw1.to(w1dt), sums[0], None, None, sums[1], sums[2],
+                dw2.to(w2dt), dwd.to(wddt), dbias)
 
 
 class BnSeluSConv(torch.autograd.Function):

@@ -13,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import sinc_x3
-from .ops import (HALF, Block0Convs, Block0Front, Block0Fused, BnSelu, ResBlockIdentity, BnSeluSConv, ResTail, SConv, SConvBnSelu, SConvBnSeluSConv, sconv_ok,
+from .ops import (HALF, Block0Convs, Block0Front, Block0Fused, BnSelu, ResBlockIdentity, ResBlockDown, BnSeluSConv, ResTail, SConv, SConvBnSelu, SConvBnSeluSConv, sconv_ok,
                   sconv_weight_ok, sincconv_absmaxpool)
 
 
@@ -159,6 +159,13 @@ class Residual_block(nn.Module):
                     # the whole block as one autograd op: the block input's gradient in one pass
                     # (conv1's input gradient + the identity branch's, radhip.ops.ResBlockIdentity)
                     return ResBlockIdentity.apply(x, self.conv1.weight, *bnp, w2, self.conv2.bias)
+                if (pair and self.downsample and sconv_ok(x, self.conv_downsample.weight)
+                        and os.environ.get("RADHIP_RES_FUSED", "1") != "0"
+                        and os.environ.get("RADHIP_SCONV_POOL", "1") != "0"):
+                    # the downsampling block as one autograd op, so that its max-pool needs no full-width tensors
+                    # (radhip.ops.ResBlockDown; RADHIP_SCONV_POOL=0: the three ops below)
+                    return ResBlockDown.apply(x, self.conv1.weight, *bnp, w2, self.conv_downsample.weight,
+                                              self.conv2.bias + self.conv_downsample.bias)
                 if pair:
                     a = SConvBnSeluSConv.apply(x, self.conv1.weight, 1, *bnp, w2)
                 else:

@@ -20,8 +20,8 @@ import sys
 # bench.py kernel-timing names -> kernel-name patterns of one launch of that operation
 OPS = {
     "wgemm": r"wgemm_kernel<", "b0x_bwd": r"b0x_bwd_kernel", "b0x_fwd": r"b0x_fwd_kernel",
-    "sconv_fwd": r"sconv_fwd_kernel<\d+, \d+, \d+, false>", "sconv_dgrad_bnselu": r"sconv_fwd_kernel<\d+, \d+, \d+, true>",
-    "sconv_wgrad": r"sconv_wgrad_kernel<", "attn_fwd": r"attn_fwd_kernel<", "attn_bwd": r"attn_bwd_fused_kernel<",
+    "sconv_fwd": r"sconv_fwd_kernel<\d+, \d+, \d+, false[,>]", "sconv_dgrad_bnselu": r"sconv_fwd_kernel<\d+, \d+, \d+, true[,>]",
+    "sconv_wgrad": r"sconv_wgrad(_pool)?_kernel<", "attn_fwd": r"attn_fwd_kernel<", "attn_bwd": r"attn_bwd_fused_kernel<",
     "selective_scan_fwd": r"scan_fwd_seg_kernel<|s2::fwd_chunk_kernel<|s2::carry_kernel<0>|s2::fwd_out_kernel<",
     "selective_scan_bwd": r"[^_]scan_bwd_kernel<|s2::bwd_chunk_kernel<|s2::carry_kernel<1>|s2::bwd_out_kernel<",
     "pgemm": r"pgemm_kernel<", "hgemm": r"hgemm_kernel<", "lgemm": r"lgemm_kernel<", "sincconv_mfma": r"sincconv_mfma_kernel",
