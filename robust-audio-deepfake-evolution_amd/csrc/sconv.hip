@@ -26,6 +26,9 @@
 // with K = positions in registers (4 waves split the tiles); both operands are read down their columns with
 // ds_read_b64_tr_b16 (the tap's column shift is a row offset into the input image). One fp32 partial per
 // workgroup, summed by a second kernel in a fixed order (deterministic, no atomics).
+#include <climits>
+#include <initializer_list>
+
 #include "common.h"
 
 namespace rdx {
@@ -677,6 +680,15 @@ __global__ void sconv_wgrad_reduce2_kernel(const float* __restrict__ part2, int6
   dw[i] = s;
 }
 
+// workgroups resident on a CU for an LDS image of smem bytes (160 KB per CU), between 1 and 4
+static int sc_per_cu(size_t smem) {
+  const int n = (int)((160 * 1024) / smem);
+  return n < 1 ? 1 : (n > 4 ? 4 : n);
+}
+
+// the weight-gradient kernel's LDS image: two dY strips and KH + 1 input rows
+static size_t sc_wgrad_smem(int ci, int co, int kh) { return (2 * (size_t)SC_P * co + (size_t)(kh + 1) * SC_XR * ci) * 2; }
+
 template <int CI, int CO, int KH, bool kBnBwd = false, bool kPool = false, bool kExpIn = false, bool kExpRes = false>
 static int sconv_fwd_launch(const SConvArgs& a, hipStream_t st) {
   // the kernel's per-utterance buffer ranges and 32-bit offsets (the sentinel SC_OOB must lie past every range)
@@ -690,8 +702,7 @@ static int sconv_fwd_launch(const SConvArgs& a, hipStream_t st) {
   // one round of resident workgroups (256 CUs x the workgroups the LDS image allows per CU: 4 at 32 x 32
   // channels, 1 at 64 x 64): split the rows when strips x N alone is fewer (each split restages the weights
   // and KH - 1 halo rows), never more (a second round would restage for nothing)
-  const int per_cu = (int)((160 * 1024) / smem) < 1 ? 1 : ((int)((160 * 1024) / smem) > 4 ? 4 : (int)((160 * 1024) / smem));
-  const int64_t slots = 256 * (int64_t)per_cu, pairs = (int64_t)strips * a.N;
+  const int64_t slots = 256 * (int64_t)sc_per_cu(smem), pairs = (int64_t)strips * a.N;
   // the row split that minimises rounds x (rows per workgroup + the restaging, ~KH + 1 row-equivalents)
   int nz = 1;
   int64_t best = -1;
@@ -714,7 +725,7 @@ static int sconv_fwd_launch(const SConvArgs& a, hipStream_t st) {
 
 template <int CI, int CO, int KH, bool kExp = false>
 static int sconv_wgrad_launch(const SWgradArgs& a, int nblk, hipStream_t st) {
-  const size_t smem = (2 * (size_t)SC_P * CO + (size_t)(KH + 1) * SC_XR * CI) * 2;
+  const size_t smem = sc_wgrad_smem(CI, CO, KH);
   if constexpr (kExp)
     hipLaunchKernelGGL((sconv_wgrad_pool_kernel<CI, CO, KH>), dim3((unsigned)nblk), dim3(SC_T), smem, st, a);
   else
@@ -727,44 +738,65 @@ static int sconv_wgrad_launch(const SWgradArgs& a, int nblk, hipStream_t st) {
 
 using namespace rdx;
 
-#define SC_DISPATCH(FN, ...)                                                                   \
-  if (ci == 32 && co == 32 && kh == 2) return FN<32, 32, 2>(__VA_ARGS__);                      \
-  if (ci == 32 && co == 64 && kh == 2) return FN<32, 64, 2>(__VA_ARGS__);                      \
-  if (ci == 64 && co == 32 && kh == 2) return FN<64, 32, 2>(__VA_ARGS__);                      \
-  if (ci == 64 && co == 64 && kh == 2) return FN<64, 64, 2>(__VA_ARGS__);                      \
-  if (ci == 32 && co == 64 && kh == 1) return FN<32, 64, 1>(__VA_ARGS__);                      \
-  if (ci == 64 && co == 32 && kh == 1) return FN<64, 32, 1>(__VA_ARGS__);                      \
-  if (ci == 32 && co == 32 && kh == 1) return FN<32, 32, 1>(__VA_ARGS__);                      \
-  if (ci == 64 && co == 64 && kh == 1) return FN<64, 64, 1>(__VA_ARGS__);                      \
-  return RDX_EUNSUPPORTED;
+// Every instantiation of the convolution and weight-gradient kernels, as lists of (ci, co, kh). SC_ALL: the plain
+// kernels. SC_SQUARE: conv1 / conv2 of the blocks without downsampling, the shapes that also have the BN + SELU
+// backward epilogue, the pool epilogue and the pooled-gradient operands. SC_DOWN_DGRAD / SC_DOWN_WGRAD: block 2's
+// conv_downsample from a pooled gradient. An entry point dispatches with SC_xxx(SC_CONV | SC_WGRAD, flags...) (the
+// kernel template's boolean flags) and asks SC_xxx(SC_HAS, 0) whether a shape is in a list.
+#define SC_ALL(X, ...)                                                                                         \
+  X(32, 32, 2, __VA_ARGS__) X(32, 64, 2, __VA_ARGS__) X(64, 32, 2, __VA_ARGS__) X(64, 64, 2, __VA_ARGS__)      \
+  X(32, 64, 1, __VA_ARGS__) X(64, 32, 1, __VA_ARGS__) X(32, 32, 1, __VA_ARGS__) X(64, 64, 1, __VA_ARGS__)
+#define SC_SQUARE(X, ...) X(32, 32, 2, __VA_ARGS__) X(64, 64, 2, __VA_ARGS__)
+#define SC_DOWN_DGRAD(X, ...) X(64, 32, 1, __VA_ARGS__)
+#define SC_DOWN_WGRAD(X, ...) X(32, 64, 1, __VA_ARGS__)
+#define SC_HAS(CI, CO, KH, ...) || (ci == CI && co == CO && kh == KH)
+#define SC_CONV(CI, CO, KH, ...) \
+  if (ci == CI && co == CO && kh == KH) return sconv_fwd_launch<CI, CO, KH, __VA_ARGS__>(a, as_stream(stream));
+#define SC_WGRAD(CI, CO, KH, ...) \
+  if (ci == CI && co == CO && kh == KH) return sconv_wgrad_launch<CI, CO, KH, __VA_ARGS__>(a, nblk, st);
+
+static bool sc_square(int ci, int co, int kh) { return false SC_SQUARE(SC_HAS, 0); }
+
+// operands the kernels read or write in 16-byte pieces: present and aligned
+static bool sc_ptrs_ok(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!p || ((uintptr_t)p & 15) != 0) return false;
+  return true;
+}
+
+// the geometry every entry point requires (N is the convolution grid's y dimension)
+static bool sc_geom_ok(int N, int H, int W, int kh, int ph, int max_n = 65535) {
+  return N > 0 && N <= max_n && H > 0 && W > 0 && ph >= 0 && ph <= kh;
+}
+
+// The launch record of a convolution x -> y with Ho = H + 2*ph - kh + 1 output rows; an entry point adds the
+// pointers of its mode (everything else stays null).
+static SConvArgs sc_args(const void* x, const void* w, void* y, int N, int H, int W, int kh, int ph) {
+  SConvArgs a{};
+  a.x = (const hst*)x;
+  a.w = (const hst*)w;
+  a.y = (hst*)y;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.ph = ph;
+  a.Ho = H + 2 * ph - kh + 1;
+  return a;
+}
 
 // y[N, Ho, W, co] = conv(x[N, H, W, ci], w) with Ho = H + 2*ph - kh + 1; w is tap-major [kh*3][co][ci] bf16.
 // With y2 (and bn = [cb | mean | invstd*gamma | beta], 4 x co fp32) also
 //   y2 = bf16(selu(((bf16(y) + cb) - mean) * invstd*gamma + beta)), exactly radhip.ops.BnSelu's forward.
 extern "C" int rdx_sconv_fwd(const void* x, const void* w, void* y, void* y2, const float* bn, int N, int H, int W,
                              int ci, int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(x) && al(w) && al(y) && (!y2 || (al(y2) && bn)));
-  SConvArgs a;
-  a.x = (const hst*)x;
-  a.w = (const hst*)w;
-  a.y = (hst*)y;
+  RDX_REQUIRE(sc_ptrs_ok({x, w, y}) && (!y2 || (sc_ptrs_ok({y2}) && bn)));
+  RDX_REQUIRE(sc_geom_ok(N, H, W, kh, ph) && (kh == 1 || kh == 2));
+  SConvArgs a = sc_args(x, w, y, N, H, W, kh, ph);
+  RDX_REQUIRE(a.Ho > 0);
   a.y2 = (hst*)y2;
   a.bn = bn;
-  a.c = nullptr;
-  a.sums = nullptr;
-  a.res = nullptr;
-  a.xarg = a.rarg = nullptr;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = ph;
-  a.Ho = H + 2 * ph - kh + 1;
-  RDX_REQUIRE(a.Ho > 0 && N <= 65535);
-  hipStream_t st = as_stream(stream);
-  SC_DISPATCH(sconv_fwd_launch, a, st)
+  SC_ALL(SC_CONV, false)
+  return RDX_EUNSUPPORTED;
 }
 
 // The same convolution with a residual added in the epilogue: y = bf16(bf16(conv(x, w)) + res), res [N, Ho, W, co]
@@ -772,28 +804,12 @@ extern "C" int rdx_sconv_fwd(const void* x, const void* w, void* y, void* y2, co
 // (autograd's separate add reads both and writes the sum: the same bits, one full-size round trip less).
 extern "C" int rdx_sconv_fwd_res(const void* x, const void* w, void* y, const void* res, int N, int H, int W, int ci,
                                  int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(x && w && y && res && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(x) && al(w) && al(y) && al(res));
-  SConvArgs a;
-  a.x = (const hst*)x;
-  a.w = (const hst*)w;
-  a.y = (hst*)y;
-  a.y2 = nullptr;
-  a.bn = nullptr;
-  a.c = nullptr;
-  a.sums = nullptr;
+  RDX_REQUIRE(sc_ptrs_ok({x, w, y, res}) && sc_geom_ok(N, H, W, kh, ph) && (kh == 1 || kh == 2));
+  SConvArgs a = sc_args(x, w, y, N, H, W, kh, ph);
+  RDX_REQUIRE(a.Ho > 0);
   a.res = (const hst*)res;
-  a.xarg = a.rarg = nullptr;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = ph;
-  a.Ho = H + 2 * ph - kh + 1;
-  RDX_REQUIRE(a.Ho > 0 && N <= 65535);
-  hipStream_t st = as_stream(stream);
-  SC_DISPATCH(sconv_fwd_launch, a, st)
+  SC_ALL(SC_CONV, false)
+  return RDX_EUNSUPPORTED;
 }
 
 // conv2's input gradient continued through conv1's frozen BN + SELU backward (Residual_block, the 32- and
@@ -803,29 +819,15 @@ extern "C" int rdx_sconv_fwd_res(const void* x, const void* w, void* y, const vo
 // unfused dO1. bn = [cb | mean | invstd*gamma | beta | invstd] (5 x co fp32); sums zeroed by the caller.
 extern "C" int rdx_sconv_dgrad_bnselu(const void* dy, const void* w, const void* c, void* dc, const float* bn,
                                       float* sums, int N, int H, int W, int ci, int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(dy && w && c && dc && bn && sums && N > 0 && H > 0 && W > 0 && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(dy) && al(w) && al(c) && al(dc) && N <= 65535);
-  if (!((ci == 32 && co == 32) || (ci == 64 && co == 64)) || kh != 2) return RDX_EUNSUPPORTED;
-  SConvArgs a;
-  a.x = (const hst*)dy;
-  a.w = (const hst*)w;
-  a.y = (hst*)dc;
-  a.y2 = nullptr;
+  RDX_REQUIRE(sc_ptrs_ok({dy, w, c, dc}) && bn && sums && sc_geom_ok(N, H, W, kh, ph));
+  if (!sc_square(ci, co, kh)) return RDX_EUNSUPPORTED;
+  SConvArgs a = sc_args(dy, w, dc, N, H, W, kh, ph);
+  RDX_REQUIRE(a.Ho > 0);
   a.bn = bn;
   a.c = (const hst*)c;
   a.sums = sums;
-  a.res = nullptr;
-  a.xarg = a.rarg = nullptr;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = ph;
-  a.Ho = H + 2 * ph - kh + 1;
-  RDX_REQUIRE(a.Ho > 0);
-  if (ci == 64) return sconv_fwd_launch<64, 64, 2, true>(a, as_stream(stream));
-  return sconv_fwd_launch<32, 32, 2, true>(a, as_stream(stream));
+  SC_SQUARE(SC_CONV, true)
+  return RDX_EUNSUPPORTED;
 }
 
 // A residual block's conv2 and tail in one pass: y[N, H-1, W/3, c] = MaxPool2d((1, 3))(bf16(conv2(x)) + idn + bias)
@@ -833,60 +835,30 @@ extern "C" int rdx_sconv_dgrad_bnselu(const void* dy, const void* w, const void*
 // the full-width convolution output. x [N, H, W, c], idn [N, H-1, W, c], c = ci = co in {32, 64}, W >= 3.
 extern "C" int rdx_sconv_fwd_pool(const void* x, const void* w, const void* idn, const float* bias, void* y,
                                   uint8_t* arg, int N, int H, int W, int ci, int co, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(x && w && idn && bias && y && arg && N > 0 && H > 1 && W > 0 && N <= 65535);
-  RDX_REQUIRE(al(x) && al(w) && al(idn) && al(y) && al(arg));
-  if (!((ci == 32 && co == 32) || (ci == 64 && co == 64)) || W < 3) return RDX_EUNSUPPORTED;
-  SConvArgs a;
-  a.x = (const hst*)x;
-  a.w = (const hst*)w;
-  a.y = (hst*)y;
-  a.y2 = nullptr;
+  const int kh = 2;
+  RDX_REQUIRE(sc_ptrs_ok({x, w, idn, y, arg}) && bias && sc_geom_ok(N, H, W, kh, 0) && H > 1);
+  if (!sc_square(ci, co, kh) || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a = sc_args(x, w, y, N, H, W, kh, 0);
   a.bn = bias;
-  a.c = nullptr;
-  a.sums = nullptr;
   a.res = (const hst*)idn;
-  a.xarg = a.rarg = nullptr;
   a.parg = arg;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = 0;
-  a.Ho = H - 1;
-  if (ci == 64) return sconv_fwd_launch<64, 64, 2, false, true>(a, as_stream(stream));
-  return sconv_fwd_launch<32, 32, 2, false, true>(a, as_stream(stream));
+  SC_SQUARE(SC_CONV, false, true)
+  return RDX_EUNSUPPORTED;
 }
 
 // rdx_sconv_fwd_res with the residual given as a pooled gradient: res = the scatter of (dp, arg) [N, Ho, W/3, co]
 // to full width (rdx_res_tail_bwd's dx), formed in the epilogue instead of being read; dbias [co] += the
 // per-channel sum of dp (rdx_res_tail_bwd's bias gradient; fp32 atomics, zeroed by the caller).
+// conv1's input gradient in the blocks without downsampling: 2 x 3, equal channel counts.
 extern "C" int rdx_sconv_fwd_res_pool(const void* x, const void* w, void* y, const void* dp, const uint8_t* arg,
                                       float* dbias, int N, int H, int W, int ci, int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(x && w && y && dp && arg && dbias && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(x) && al(w) && al(y) && al(dp) && al(arg));
-  SConvArgs a;
-  a.x = (const hst*)x;
-  a.w = (const hst*)w;
-  a.y = (hst*)y;
-  a.y2 = nullptr;
-  a.bn = nullptr;
-  a.c = nullptr;
+  RDX_REQUIRE(sc_ptrs_ok({x, w, y, dp, arg}) && dbias && sc_geom_ok(N, H, W, kh, ph) && (kh == 1 || kh == 2));
+  SConvArgs a = sc_args(x, w, y, N, H, W, kh, ph);
+  RDX_REQUIRE(a.Ho > 0);
   a.sums = dbias;
   a.res = (const hst*)dp;
-  a.xarg = nullptr;
   a.rarg = arg;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = ph;
-  a.Ho = H + 2 * ph - kh + 1;
-  RDX_REQUIRE(a.Ho > 0 && N <= 65535);
-  // conv1's input gradient in the blocks without downsampling: 2 x 3, equal channel counts
-  if (kh != 2 || ci != co) return RDX_EUNSUPPORTED;
-  if (ci == 64) return sconv_fwd_launch<64, 64, 2, false, false, false, true>(a, as_stream(stream));
-  if (ci == 32) return sconv_fwd_launch<32, 32, 2, false, false, false, true>(a, as_stream(stream));
+  SC_SQUARE(SC_CONV, false, false, false, true)
   return RDX_EUNSUPPORTED;
 }
 
@@ -895,30 +867,29 @@ extern "C" int rdx_sconv_fwd_res_pool(const void* x, const void* w, void* y, con
 extern "C" int rdx_sconv_dgrad_bnselu_pool(const void* dp, const uint8_t* arg, const void* w, const void* c, void* dc,
                                            const float* bn, float* sums, int N, int H, int W, int ci, int co, int kh,
                                            int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(dp && arg && w && c && dc && bn && sums && N > 0 && H > 0 && W > 0 && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(dp) && al(arg) && al(w) && al(c) && al(dc) && N <= 65535);
-  if (!((ci == 32 && co == 32) || (ci == 64 && co == 64)) || kh != 2 || W < 3) return RDX_EUNSUPPORTED;
-  SConvArgs a;
-  a.x = (const hst*)dp;
-  a.w = (const hst*)w;
-  a.y = (hst*)dc;
-  a.y2 = nullptr;
+  RDX_REQUIRE(sc_ptrs_ok({dp, arg, w, c, dc}) && bn && sums && sc_geom_ok(N, H, W, kh, ph));
+  if (!sc_square(ci, co, kh) || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a = sc_args(dp, w, dc, N, H, W, kh, ph);
+  RDX_REQUIRE(a.Ho > 0);
   a.bn = bn;
   a.c = (const hst*)c;
   a.sums = sums;
-  a.res = nullptr;
   a.xarg = arg;
-  a.rarg = nullptr;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = ph;
-  a.Ho = H + 2 * ph - kh + 1;
-  RDX_REQUIRE(a.Ho > 0);
-  if (ci == 64) return sconv_fwd_launch<64, 64, 2, true, false, true>(a, as_stream(stream));
-  return sconv_fwd_launch<32, 32, 2, true, false, true>(a, as_stream(stream));
+  SC_SQUARE(SC_CONV, true, false, true)
+  return RDX_EUNSUPPORTED;
+}
+
+// The input gradient of block 2's conv_downsample (1 x 3, 32 -> 64 channels) from the pooled gradient (dp, arg)
+// [N, H, W/3, 64] of its output: rdx_sconv_fwd of rdx_res_tail_bwd's scatter with the flipped kernel w [3][32][64],
+// expanded while it is staged. ci = 64 (the gradient's channels), co = 32, kh = 1, ph = 0; dx [N, H, W, 32].
+extern "C" int rdx_sconv_dgrad_pool(const void* dp, const uint8_t* arg, const void* w, void* dx, int N, int H, int W,
+                                    int ci, int co, int kh, int ph, void* stream) {
+  RDX_REQUIRE(sc_ptrs_ok({dp, arg, w, dx}) && sc_geom_ok(N, H, W, 1, 0));
+  if (ph != 0 || W < 3) return RDX_EUNSUPPORTED;
+  SConvArgs a = sc_args(dp, w, dx, N, H, W, 1, 0);
+  a.xarg = arg;
+  SC_DOWN_DGRAD(SC_CONV, false, false, true)
+  return RDX_EUNSUPPORTED;
 }
 
 // Both 16-bit operand layouts of up to SC_WP_MAX convolution weights [co][ci][kh][3] (fp32) in one launch: wf
@@ -986,47 +957,25 @@ static int sc_wgrad_blocks(int N, int Ho, int W) {
 // rows of kh*3*co*ci fp32 the weight-gradient scratch needs: one partial per workgroup + the reduction slices
 extern "C" int rdx_sconv_wgrad_nblk(int N, int Ho, int W) { return sc_wgrad_blocks(N, Ho, W) + SC_RS; }
 
-// The input gradient of block 2's conv_downsample (1 x 3, 32 -> 64 channels) from the pooled gradient (dp, arg)
-// [N, H, W/3, 64] of its output: rdx_sconv_fwd of rdx_res_tail_bwd's scatter with the flipped kernel w [3][32][64],
-// expanded while it is staged. ci = 64 (the gradient's channels), co = 32, kh = 1, ph = 0; dx [N, H, W, 32].
-extern "C" int rdx_sconv_dgrad_pool(const void* dp, const uint8_t* arg, const void* w, void* dx, int N, int H, int W,
-                                    int ci, int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(dp && arg && w && dx && N > 0 && H > 0 && W > 0 && N <= 65535);
-  RDX_REQUIRE(al(dp) && al(arg) && al(w) && al(dx));
-  if (ci != 64 || co != 32 || kh != 1 || ph != 0 || W < 3) return RDX_EUNSUPPORTED;
-  SConvArgs a;
-  a.x = (const hst*)dp;
-  a.w = (const hst*)w;
-  a.y = (hst*)dx;
-  a.y2 = nullptr;
-  a.bn = nullptr;
-  a.c = nullptr;
-  a.sums = nullptr;
-  a.res = nullptr;
-  a.xarg = arg;
-  a.rarg = nullptr;
-  a.parg = nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.ph = 0;
-  a.Ho = H;
-  return sconv_fwd_launch<64, 32, 1, false, false, true>(a, as_stream(stream));
-}
-
 // dw [kh*3][co][ci] fp32 = sum over positions of dy (x) shifted x; part: [nblk][kh*3*co*ci] fp32 scratch,
 // nblk = rdx_sconv_wgrad_nblk(N, Ho, W).
-// arg != NULL: dy is a pooled gradient (dy, arg) [N, Ho, W/3, co]
+// arg != NULL: dy is a pooled gradient (dy, arg) [N, Ho, W/3, co]: conv2 (SC_SQUARE) or block 2's conv_downsample
+static int sc_wgrad_launch_for(const SWgradArgs& a, int nblk, int ci, int co, int kh, hipStream_t st) {
+  if (a.arg) {
+    SC_SQUARE(SC_WGRAD, true)
+    SC_DOWN_WGRAD(SC_WGRAD, true)
+    return RDX_EUNSUPPORTED;
+  }
+  SC_ALL(SC_WGRAD, false)
+  return RDX_EUNSUPPORTED;
+}
+
 static int sc_wgrad_run(const void* x, const void* dy, const uint8_t* arg, float* dw, float* part, int N,
                         int H, int W, int ci, int co, int kh, int ph, void* stream) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  RDX_REQUIRE(x && dy && dw && part && N > 0 && H > 0 && W > 0 && (kh == 1 || kh == 2) && ph >= 0 && ph <= kh);
-  RDX_REQUIRE(al(x) && al(dy) && (!arg || al(arg)));
-  // pooled gradients: conv2 (2 x 3, equal channels) and block 2's conv_downsample (1 x 3, 32 -> 64)
-  if (arg && (W < 3 || !((ci == co && kh == 2 && (ci == 32 || ci == 64)) || (ci == 32 && co == 64 && kh == 1))))
-    return RDX_EUNSUPPORTED;
-  SWgradArgs a;
+  RDX_REQUIRE(sc_ptrs_ok({x, dy}) && dw && part && sc_geom_ok(N, H, W, kh, ph, INT_MAX) && (kh == 1 || kh == 2));
+  RDX_REQUIRE(!arg || sc_ptrs_ok({arg}));
+  if (arg && (W < 3 || !(false SC_SQUARE(SC_HAS, 0) SC_DOWN_WGRAD(SC_HAS, 0)))) return RDX_EUNSUPPORTED;
+  SWgradArgs a{};
   a.x = (const hst*)x;
   a.dy = (const hst*)dy;
   a.arg = arg;
@@ -1044,23 +993,10 @@ static int sc_wgrad_run(const void* x, const void* dy, const uint8_t* arg, float
   a.units = (int64_t)N * a.strips * a.nz;
   // one resident round of workgroups (the LDS image sets how many fit on a CU), each walking several units:
   // fewer workgroups write fewer fp32 partials (kh*3*co*ci each: 96 KB at 64 x 64 channels) for the reduction
-  const int64_t smem = (2 * (int64_t)SC_P * co + (int64_t)(kh + 1) * SC_XR * ci) * 2;
-  const int per_cu = (int)((160 * 1024) / smem) < 1 ? 1 : ((int)((160 * 1024) / smem) > 4 ? 4 : (int)((160 * 1024) / smem));
-  const int cap = sc_wgrad_blocks(N, a.Ho, W);
-  const int nblk = cap < 256 * per_cu ? cap : 256 * per_cu;
+  const int cap = sc_wgrad_blocks(N, a.Ho, W), round = 256 * sc_per_cu(sc_wgrad_smem(ci, co, kh));
+  const int nblk = cap < round ? cap : round;
   hipStream_t st = as_stream(stream);
-  int rc = RDX_EUNSUPPORTED;
-  if (arg && kh == 1) rc = sconv_wgrad_launch<32, 64, 1, true>(a, nblk, st);
-  else if (arg && ci == 32) rc = sconv_wgrad_launch<32, 32, 2, true>(a, nblk, st);
-  else if (arg) rc = sconv_wgrad_launch<64, 64, 2, true>(a, nblk, st);
-  else if (ci == 32 && co == 32 && kh == 2) rc = sconv_wgrad_launch<32, 32, 2>(a, nblk, st);
-  else if (ci == 32 && co == 64 && kh == 2) rc = sconv_wgrad_launch<32, 64, 2>(a, nblk, st);
-  else if (ci == 64 && co == 32 && kh == 2) rc = sconv_wgrad_launch<64, 32, 2>(a, nblk, st);
-  else if (ci == 64 && co == 64 && kh == 2) rc = sconv_wgrad_launch<64, 64, 2>(a, nblk, st);
-  else if (ci == 32 && co == 64 && kh == 1) rc = sconv_wgrad_launch<32, 64, 1>(a, nblk, st);
-  else if (ci == 64 && co == 32 && kh == 1) rc = sconv_wgrad_launch<64, 32, 1>(a, nblk, st);
-  else if (ci == 32 && co == 32 && kh == 1) rc = sconv_wgrad_launch<32, 32, 1>(a, nblk, st);
-  else if (ci == 64 && co == 64 && kh == 1) rc = sconv_wgrad_launch<64, 64, 1>(a, nblk, st);
+  const int rc = sc_wgrad_launch_for(a, nblk, ci, co, kh, st);
   if (rc != RDX_OK) return rc;
   const int64_t n = (int64_t)kh * 3 * co * ci;
   float* part2 = part + (int64_t)nblk * n;  // SC_RS more rows of the scratch

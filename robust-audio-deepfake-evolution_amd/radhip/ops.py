@@ -689,6 +689,56 @@ def _nhwc(t):
     return t.contiguous(memory_format=torch.channels_last)
 
 
+def _empty_nhwc(shape, like, dtype=None):
+    """An uninitialised channels_last [N, C, H, W] tensor on like's device, of like's dtype unless one is given."""
+    return torch.empty(shape, device=like.device, dtype=dtype or like.dtype, memory_format=torch.channels_last)
+
+
+def _f32_rows(*ts):
+    return [t.detach().contiguous().float() for t in ts]
+
+
+def _bnselu_fwd(c, f32):
+    """selu(frozen_bn(c + conv_bias)), f32 = (conv_bias, mean, invstd, gamma, beta) fp32 rows."""
+    N, C, H, W = c.shape
+    y = torch.empty_like(c)
+    check(_L(c).rdx_bnselu_fwd(_dtype_code(c), _p(c), *[_p(t) for t in f32], _p(y), N * H * W, C, _stream(c)),
+          "bnselu_fwd")
+    return y
+
+
+def _bnselu_bwd(c, dy, f32):
+    """_bnselu_fwd's backward: dc and the channel sums [3][C] (d conv_bias, d gamma, d beta; fp32 atomics)."""
+    N, C, H, W = c.shape
+    dc = torch.empty_like(c)
+    sums = torch.zeros(3, C, device=c.device, dtype=torch.float32)
+    check(_L(c).rdx_bnselu_bwd(_dtype_code(c), _p(c), _p(dy), *[_p(t) for t in f32], _p(dc), _p(sums), N * H * W, C,
+                               _stream(c)), "bnselu_bwd")
+    return dc, sums
+
+
+def _res_tail_fwd(a, idn, bias):
+    """y = MaxPool2d((1, 3))(a + idn + bias) and its window index bytes; a, idn NHWC of one dtype, bias fp32 [C]."""
+    if idn.shape != a.shape:
+        raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(idn.shape)}")
+    N, C, H, W = a.shape
+    y = _empty_nhwc((N, C, H, W // 3), a)
+    arg = _empty_nhwc((N, C, H, W // 3), a, torch.uint8)
+    check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(idn), _p(bias), _p(y), _p(arg), N * H, W, C, _stream(a)),
+          "res_tail_fwd")
+    return y, arg
+
+
+def _res_tail_bwd(dy, arg, shape):
+    """The pool gradient scattered to the full-width `shape` (the gradient of a and of idn) and the bias gradient."""
+    N, C, H, W = shape
+    ds = _empty_nhwc(shape, dy)
+    dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
+    check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C, _stream(dy)),
+          "res_tail_bwd")
+    return ds, dbias
+
+
 class BnSelu(torch.autograd.Function):
     """selu(frozen_bn(c + conv_bias)) on an NHWC [N, C, H, W] tensor (conv1 run without its bias)."""
 
@@ -696,23 +746,14 @@ class BnSelu(torch.autograd.Function):
     def forward(ctx, c, conv_bias, mean, invstd, weight, bias):
         _require_gpu(c)
         c = _nhwc(c)
-        N, C, H, W = c.shape
-        f32 = [t.detach().contiguous().float() for t in (conv_bias, mean, invstd, weight, bias)]
-        y = torch.empty_like(c)
-        check(_L(c).rdx_bnselu_fwd(_dtype_code(c), _p(c), *[_p(t) for t in f32], _p(y), N * H * W, C, _stream(c)),
-              "bnselu_fwd")
+        f32 = _f32_rows(conv_bias, mean, invstd, weight, bias)
         ctx.save_for_backward(c, *f32)
-        return y
+        return _bnselu_fwd(c, f32)
 
     @staticmethod
     def backward(ctx, dy):
-        c, cb, mean, invstd, w, b = ctx.saved_tensors
-        N, C, H, W = c.shape
-        dy = _nhwc(dy.to(c.dtype))
-        dc = torch.empty_like(c)
-        sums = torch.zeros(3, C, device=c.device, dtype=torch.float32)
-        check(_L(c).rdx_bnselu_bwd(_dtype_code(c), _p(c), _p(dy), _p(cb), _p(mean), _p(invstd), _p(w), _p(b), _p(dc),
-                                   _p(sums), N * H * W, C, _stream(c)), "bnselu_bwd")
+        c, *f32 = ctx.saved_tensors
+        dc, sums = _bnselu_bwd(c, _nhwc(dy.to(c.dtype)), f32)
         return dc, sums[0], None, None, sums[1], sums[2]
 
 
@@ -724,28 +765,52 @@ class ResTail(torch.autograd.Function):
     def forward(ctx, a, identity, bias):
         _require_gpu(a, identity)
         a, identity = _nhwc(a), _nhwc(identity.to(a.dtype))
-        N, C, H, W = a.shape
-        if identity.shape != a.shape:
-            raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(identity.shape)}")
-        y = torch.empty(N, C, H, W // 3, device=a.device, dtype=a.dtype, memory_format=torch.channels_last)
-        arg = torch.empty(N, C, H, W // 3, device=a.device, dtype=torch.uint8, memory_format=torch.channels_last)
-        bf = bias.detach().contiguous().float()
-        check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(identity), _p(bf), _p(y), _p(arg), N * H, W, C,
-                                     _stream(a)), "res_tail_fwd")
+        y, arg = _res_tail_fwd(a, identity, *_f32_rows(bias))
         ctx.save_for_backward(arg)
-        ctx.shape, ctx.dtype = (N, C, H, W), a.dtype
+        ctx.shape, ctx.dtype = tuple(a.shape), a.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (arg,) = ctx.saved_tensors
-        N, C, H, W = ctx.shape
-        dy = _nhwc(dy.to(ctx.dtype))
-        dx = torch.empty(N, C, H, W, device=dy.device, dtype=ctx.dtype, memory_format=torch.channels_last)
-        dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
-        check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(dx), _p(dbias), N * H, W, C, _stream(dy)),
-              "res_tail_bwd")
+        dx, dbias = _res_tail_bwd(_nhwc(dy.to(ctx.dtype)), arg, ctx.shape)
         return dx, dx, dbias
+
+
+def _b0_prep(x, w1, wd):
+    """Block 0's operands as its kernels take them: x in the 16-bit autocast dtype (one channel: [N, H, W] in memory)
+    and the 16-bit-rounded weights of conv1 [C][6] and conv_downsample [C][3] in fp32."""
+    hd = half_dtype()
+    C = w1.shape[0]
+    return (x.to(hd).contiguous(), w1.detach().to(hd).float().reshape(C, 6).contiguous(),
+            wd.detach().to(hd).float().reshape(C, 3).contiguous())
+
+
+def _b0_fwd(xb, w1b, wdb, bn5):
+    """c = conv1(x), out1 = selu(frozen_bn(c + conv1_bias)) and idn = conv_downsample(x) of block 0 in one pass."""
+    N, _, H, W = xb.shape
+    C = w1b.shape[0]
+    c = _empty_nhwc((N, C, H + 1, W), xb)
+    out1 = torch.empty_like(c)
+    idn = _empty_nhwc((N, C, H, W), xb)
+    with _timed("sincnet_b0_fwd", xb, 2.0 * (xb.numel() + 2 * c.numel() + idn.numel())):
+        check(_L(xb).rdx_sincnet_b0_fwd(_p(xb), _p(w1b), _p(wdb), _p(bn5), _p(c), _p(out1), _p(idn), N, H, W, C,
+                                       _stream(xb)), "sincnet_b0_fwd")
+    return c, out1, idn
+
+
+def _b0_bwd(xb, dc, di, w1b, wdb, shapes):
+    """Both block-0 convolutions' backward in one pass: dx [N, 1, H, W] fp32 and the weight gradients in the
+    shapes (conv1.weight's, conv_downsample.weight's)."""
+    N, _, H, W = xb.shape
+    C = shapes[0][0]
+    dx = torch.empty(N, 1, H, W, device=xb.device, dtype=torch.float32)
+    part = torch.empty(lib().rdx_sincnet_b0_nblk(N * H * W), C * 9, device=xb.device, dtype=torch.float32)
+    with _timed("sincnet_b0_bwd", dc, 2 * (dc.numel() + di.numel()) + 4 * dx.numel() + 2 * xb.numel()):
+        check(_L(xb).rdx_sincnet_b0_bwd(_p(xb), _p(dc), _p(di), _p(w1b), _p(wdb), _p(dx), _p(part), N, H, W, C,
+                                       _stream(dc)), "sincnet_b0_bwd")
+    dw = part.sum(0).view(C, 9)
+    return dx, dw[:, :6].reshape(shapes[0]), dw[:, 6:].reshape(shapes[1])
 
 
 class Block0Convs(torch.autograd.Function):
@@ -771,30 +836,27 @@ class Block0Convs(torch.autograd.Function):
     def backward(ctx, dc, di):
         xb, w1b, wdb = ctx.saved_tensors
         w1_shape, wd_shape, x_dtype = ctx.meta
-        N, _, H, W = xb.shape
-        C = w1_shape[0]
         dc = _nhwc(dc.to(xb.dtype))
         di = _nhwc(di.to(xb.dtype))
         xc = xb.contiguous(memory_format=torch.channels_last)      # one channel: [N, H, W] in memory
-        w1f = w1b.float().contiguous()                               # the 16-bit weights the forward used
-        wdf = wdb.float().contiguous()
-        dx = torch.empty(N, 1, H, W, device=xb.device, dtype=torch.float32)
-        part = torch.empty(lib().rdx_sincnet_b0_nblk(N * H * W), C * 9, device=xb.device, dtype=torch.float32)
-        with _timed("sincnet_b0_bwd", dc, 2 * (dc.numel() + di.numel()) + 4 * dx.numel() + 2 * xc.numel()):
-            check(_L(xb).rdx_sincnet_b0_bwd(_p(xc), _p(dc), _p(di), _p(w1f), _p(wdf), _p(dx), _p(part), N, H, W, C,
-                                           _stream(dc)), "sincnet_b0_bwd")
-        dw = part.sum(0).view(C, 9)
-        return dx.to(x_dtype), dw[:, :6].reshape(w1_shape), dw[:, 6:].reshape(wd_shape)
+        # the 16-bit weights the forward used
+        dx, dw1, dwd = _b0_bwd(xc, dc, di, w1b.float().contiguous(), wdb.float().contiguous(), (w1_shape, wd_shape))
+        return dx.to(x_dtype), dw1, dwd
 
 
 # ------------------------------------------------------------- SincNet residual convolutions ----
 SCONV_CH = (32, 64)
 
 
+def sconv_enabled():
+    """RADHIP_SCONV=0: no convolution runs on csrc/sconv.hip."""
+    return os.environ.get("RADHIP_SCONV", "1") != "0"
+
+
 def sconv_weight_ok(weight):
     """The kernels csrc/sconv.hip has: C_in and C_out in {32, 64}, kernel (1|2) x 3 (RADHIP_SCONV=0: none)."""
     co, ci, kh, kw = weight.shape
-    return ci in SCONV_CH and co in SCONV_CH and kh in (1, 2) and kw == 3 and os.environ.get("RADHIP_SCONV", "1") != "0"
+    return ci in SCONV_CH and co in SCONV_CH and kh in (1, 2) and kw == 3 and sconv_enabled()
 
 
 def sconv_ok(x, weight):
@@ -861,7 +923,7 @@ def _sconv_run(x, w_tap, ci, co, kh, ph, y2=None, bn=None, res=None):
     tensor of x's dtype added in the epilogue (y = r(r(conv) + res), r = rounding to that dtype)."""
     N, _, H, W = x.shape
     Ho = H + 2 * ph - kh + 1
-    y = torch.empty(N, co, Ho, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _empty_nhwc((N, co, Ho, W), x)
     # algorithmic HBM bytes (the convolution is HBM-bound: ~100 FLOP per byte at these channel counts)
     nbytes = 2.0 * (N * H * W * ci + N * Ho * W * co * (2 if (y2 is not None or res is not None) else 1))
     with _timed("sconv_fwd", x, nbytes, shape=(N, H, W, ci, co, kh, ph)):
@@ -897,8 +959,8 @@ def _sconv_run_pool(x, w_tap, idn, bias, c):
     Ho = H - 1
     if idn.shape != (N, c, Ho, W) or idn.dtype != x.dtype or not idn.is_contiguous(memory_format=torch.channels_last):
         raise ValueError("radhip sconv: identity must be NHWC of the convolution output's shape and dtype")
-    y = torch.empty(N, c, Ho, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-    arg = torch.empty(N, c, Ho, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
+    y = _empty_nhwc((N, c, Ho, W // 3), x)
+    arg = _empty_nhwc((N, c, Ho, W // 3), x, torch.uint8)
     # x and the identity in, a third of a full-width output (+ one index byte per element) out
     nbytes = 2.0 * (N * H * W * c + N * Ho * W * c) + 3.0 * y.numel()
     with _timed("sconv_fwd", x, nbytes, shape=(N, H, W, c, c, 2, 0)):
@@ -912,7 +974,7 @@ def _sconv_run_res_pool(x, w_tap, dp, arg, dbias, ci, co, kh, ph):
     receives dp's per-channel sum."""
     N, _, H, W = x.shape
     Ho = H + 2 * ph - kh + 1
-    y = torch.empty(N, co, Ho, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    y = _empty_nhwc((N, co, Ho, W), x)
     nbytes = 2.0 * (N * H * W * ci + N * Ho * W * co) + 3.0 * dp.numel()
     with _timed("sconv_fwd", x, nbytes, shape=(N, H, W, ci, co, kh, ph)):
         check(_L(x).rdx_sconv_fwd_res_pool(_p(x), _p(w_tap), _p(y), _p(dp), _p(arg), _p(dbias), N, H, W, ci, co, kh, ph,
@@ -940,7 +1002,7 @@ def _sconv_dgrad_pool(dp, arg, wd, weight_shape, W):
     pooled gradient (dp, arg) [N, 64, H, W // 3] of its output; wd: the flipped kernel [3][ci][co]."""
     co, ci, kh, kw = weight_shape
     N, _, H, _ = dp.shape
-    dx = torch.empty(N, ci, H, W, device=dp.device, dtype=dp.dtype, memory_format=torch.channels_last)
+    dx = _empty_nhwc((N, ci, H, W), dp)
     with _timed("sconv_fwd", dp, 3.0 * dp.numel() + 2.0 * dx.numel(), shape=(N, H, W, co, ci, kh, 0)):
         check(_L(dp).rdx_sconv_dgrad_pool(_p(dp), _p(arg), _p(wd), _p(dx), N, H, W, co, ci, kh, 0, _stream(dp)),
               "sconv_dgrad_pool")
@@ -1000,11 +1062,10 @@ class SConvBnSelu(torch.autograd.Function):
         x = _nhwc(x.to(half_dtype()))
         co, ci, kh, _ = weight.shape
         wf, wd = _sconv_w(weight, x.dtype)
-        f32 = [t.detach().contiguous().float() for t in (conv_bias, mean, invstd, gamma, beta)]
+        f32 = _f32_rows(conv_bias, mean, invstd, gamma, beta)
         bn = torch.stack([f32[0], f32[1], f32[2] * f32[3], f32[4]]).contiguous()
         N, _, H, W = x.shape
-        y = torch.empty(N, co, H + 2 * ph - kh + 1, W, device=x.device, dtype=x.dtype,
-                        memory_format=torch.channels_last)
+        y = _empty_nhwc((N, co, H + 2 * ph - kh + 1, W), x)
         c = _sconv_run(x, wf, ci, co, kh, ph, y2=y, bn=bn)
         ctx.save_for_backward(x, wd, c, *f32)
         ctx.meta = (tuple(weight.shape), ph, weight.dtype)
@@ -1012,14 +1073,9 @@ class SConvBnSelu(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, wd, c, cb, mean, invstd, w, b = ctx.saved_tensors
+        x, wd, c, *f32 = ctx.saved_tensors
         shape, ph, wdt = ctx.meta
-        N, C, H, W = c.shape
-        dy = _nhwc(dy.to(c.dtype))
-        dc = torch.empty_like(c)
-        sums = torch.zeros(3, C, device=c.device, dtype=torch.float32)
-        check(_L(c).rdx_bnselu_bwd(_dtype_code(c), _p(c), _p(dy), _p(cb), _p(mean), _p(invstd), _p(w), _p(b), _p(dc),
-                                   _p(sums), N * H * W, C, _stream(c)), "bnselu_bwd")
+        dc, sums = _bnselu_bwd(c, _nhwc(dy.to(c.dtype)), f32)
         dx, dw = _sconv_backward(x, dc, wd, shape, ph, ctx.needs_input_grad[0])
         return dx, dw.to(wdt), None, sums[0], None, None, sums[1], sums[2]
 
@@ -1038,28 +1094,38 @@ def _conv2_grad_to_c(da, out1, c, wd2, w2_shape, bn5, f32, arg=None):
     kernels expand it while they stage it."""
     co2, ci2, kh2, _ = w2_shape
     N, C, Ho, W = c.shape
+    H = da.shape[2]
+    if arg is None and not _fused_dgrad_bn_ok(w2_shape):
+        dc, sums = _bnselu_bwd(c, _sconv_run(da, wd2, co2, ci2, kh2, kh2 - 1), f32)
+        return dc, sums, _sconv_backward(out1, da, wd2, w2_shape, 0, False)[1]
     dc = torch.empty_like(c)
     sums = torch.zeros(3, C, device=c.device, dtype=torch.float32)
     if arg is not None:
-        H = da.shape[2]
         nbytes = 3.0 * da.numel() + 2.0 * (2 * N * Ho * W * C)
         with _timed("sconv_dgrad_bnselu", da, nbytes, shape=(N, H, W)):
             check(_L(da).rdx_sconv_dgrad_bnselu_pool(_p(da), _p(arg), _p(wd2), _p(c), _p(dc), _p(bn5), _p(sums), N, H, W,
                                                     co2, ci2, kh2, kh2 - 1, _stream(da)), "sconv_dgrad_bnselu_pool")
         return dc, sums, _sconv_wgrad_pool(out1, da, arg, w2_shape)
-    if _fused_dgrad_bn_ok(w2_shape):
-        H = da.shape[2]
-        nbytes = 2.0 * (N * H * W * co2 + 2 * N * Ho * W * C)
-        with _timed("sconv_dgrad_bnselu", da, nbytes, shape=(N, H, W)):
-            check(_L(da).rdx_sconv_dgrad_bnselu(_p(da), _p(wd2), _p(c), _p(dc), _p(bn5), _p(sums), N, H, W, co2, ci2,
-                                               kh2, kh2 - 1, _stream(da)), "sconv_dgrad_bnselu")
-    else:
-        do1 = _sconv_run(da, wd2, co2, ci2, kh2, kh2 - 1)
-        cb, mean, invstd, w, b = f32
-        check(_L(c).rdx_bnselu_bwd(_dtype_code(c), _p(c), _p(do1), _p(cb), _p(mean), _p(invstd), _p(w), _p(b),
-                                   _p(dc), _p(sums), N * Ho * W, C, _stream(c)), "bnselu_bwd")
+    nbytes = 2.0 * (N * H * W * co2 + 2 * N * Ho * W * C)
+    with _timed("sconv_dgrad_bnselu", da, nbytes, shape=(N, H, W)):
+        check(_L(da).rdx_sconv_dgrad_bnselu(_p(da), _p(wd2), _p(c), _p(dc), _p(bn5), _p(sums), N, H, W, co2, ci2,
+                                           kh2, kh2 - 1, _stream(da)), "sconv_dgrad_bnselu")
     _, dw2 = _sconv_backward(out1, da, wd2, w2_shape, 0, False)
     return dc, sums, dw2
+
+
+def _frozen_invstd(bn):
+    """rsqrt(running_var + eps) of a frozen BatchNorm, once per accumulation window (SCONV_WCACHE)."""
+    cache = SCONV_WCACHE
+    if cache is None:
+        return torch.rsqrt(bn.running_var + bn.eps)
+    key = ("invstd", id(bn.running_var))
+    hit = cache.get(key)
+    if hit is not None and hit[0] is bn.running_var:
+        return hit[1]
+    v = torch.rsqrt(bn.running_var + bn.eps)
+    cache[key] = (bn.running_var, v)
+    return v
 
 
 def _bn_rows(conv_bias, mean, invstd, gamma, beta):
@@ -1094,8 +1160,7 @@ class SConvBnSeluSConv(torch.autograd.Function):
         wf2, wd2 = _sconv_w(w2, x.dtype)
         f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
         N, _, H, W = x.shape
-        out1 = torch.empty(N, co, H + 2 * ph1 - kh + 1, W, device=x.device, dtype=x.dtype,
-                           memory_format=torch.channels_last)
+        out1 = _empty_nhwc((N, co, H + 2 * ph1 - kh + 1, W), x)
         c = _sconv_run(x, wf1, ci, co, kh, ph1, y2=out1, bn=bn5[:4])
         co2, ci2, kh2, _ = w2.shape
         a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
@@ -1113,137 +1178,79 @@ class SConvBnSeluSConv(torch.autograd.Function):
         return dx, dw1.to(w1dt), None, sums[0], None, None, sums[1], sums[2], dw2.to(w2dt)
 
 
-class ResBlockIdentity(torch.autograd.Function):
-    """A residual block without downsampling (SincNet blocks 1, 3-5: Residual_block.forward,
-    src/models/DualStreamSEMamba.py:182-200, frozen BN): MaxPool2d((1, 3))(conv2(selu(bn2(conv1(x) + cb))) + x + b2)
-    as one autograd op. Forward: SConvBnSeluSConv's and ResTail's kernels. Backward: ResTail's scatter, conv2's input
-    gradient with the BN + SELU backward, then the block input's gradient in ONE pass, conv1's input gradient with
-    the identity branch's gradient added in its epilogue (rdx_sconv_fwd_res): the bits autograd's separate add of
-    the two full-size gradients produces, without that read-read-write pass. Where sconv_pool_ok, conv2's launch does
-    the residual sum and the pool in its epilogue (no full-width conv2 output, no ResTail launch) and the backward
-    kernels take the pool's gradient as (dy, argmax byte) instead of ResTail's full-width scatter: the same bits."""
+class ResBlock(torch.autograd.Function):
+    """A residual block past block 0 as one autograd op (Residual_block.forward,
+    src/models/DualStreamSEMamba.py:182-200, frozen BN): MaxPool2d((1, 3))(conv2(selu(bn2(conv1(x) + cb))) + idn + bias).
+    wdn None (SincNet blocks 1, 3-5): idn is the block input x and bias conv2's; with wdn (block 2, 32 -> 64 channels)
+    idn = conv_downsample(x) on csrc/sconv.hip and bias the sum of both convolutions' biases.
+    Forward: conv1 with the BN + SELU epilogue, conv_downsample, then conv2 with the residual sum and the pool in its
+    epilogue (sconv_pool_ok "fwd": no full-width conv2 output, no tail launch; otherwise conv2 and rdx_res_tail_fwd).
+    Backward: the pool gradient stays (dy, argmax byte) for the kernels that consume it (sconv_pool_ok "bwd";
+    otherwise rdx_res_tail_bwd's full-width scatter feeds the plain kernels), conv2's input gradient runs with the
+    BN + SELU backward, and the block input's gradient is ONE pass, conv1's input gradient with the identity branch's
+    added in its epilogue (rdx_sconv_fwd_res; pooled and without wdn rdx_sconv_fwd_res_pool, which also sums the bias
+    gradient): the bits autograd's separate add of the two full-size gradients produces, without that
+    read-read-write pass. The same bits as SConvBnSeluSConv (+ SConv) + ResTail; with wdn the pooled bias gradient is
+    a reduction over the pooled tensor."""
 
     @staticmethod
-    def forward(ctx, x, w1, conv_bias, mean, invstd, gamma, beta, w2, b2):
+    def forward(ctx, x, w1, conv_bias, mean, invstd, gamma, beta, w2, bias, wdn):
         _require_gpu(x)
         x_dtype = x.dtype
         x = _nhwc(x.to(half_dtype()))
         co, ci, kh, _ = w1.shape
         wf1, wd1 = _sconv_w(w1, x.dtype)
         wf2, wd2 = _sconv_w(w2, x.dtype)
+        wfd, wdd = _sconv_w(wdn, x.dtype) if wdn is not None else (None, None)
         f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
         N, _, H, W = x.shape
-        out1 = torch.empty(N, co, H + 1, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+        out1 = _empty_nhwc((N, co, H + 1, W), x)
         c = _sconv_run(x, wf1, ci, co, kh, 1, y2=out1, bn=bn5[:4])
         co2, ci2, kh2, _ = w2.shape
-        bf = b2.detach().contiguous().float()
-        if sconv_pool_ok(w2.shape, W, "fwd") and (N, co2, H + 2 - kh2, W) == tuple(x.shape):
-            # conv2 with the residual sum and the max-pool in its epilogue: its full-width output is never stored
-            y, arg = _sconv_run_pool(out1, wf2, x, bf, co2)
-        else:
-            a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
-            if a.shape != x.shape:
-                raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(x.shape)}")
-            y = torch.empty(N, co2, H, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-            arg = torch.empty(N, co2, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
-            check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(x), _p(bf), _p(y), _p(arg), N * H, W, co2,
-                                         _stream(a)), "res_tail_fwd")
-        ctx.save_for_backward(x, wd1, c, out1, wd2, bn5, arg, *f32)
-        ctx.meta = (tuple(w1.shape), w1.dtype, tuple(w2.shape), w2.dtype, x_dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, wd1, c, out1, wd2, bn5, arg, *f32 = ctx.saved_tensors
-        s1, w1dt, s2, w2dt, x_dtype = ctx.meta
-        N, C, H, W = x.shape
-        dy = _nhwc(dy.to(x.dtype))
-        dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
-        co, ci, kh, _ = s1
-        if (sconv_pool_ok(s2, W, "bwd") and _fused_dgrad_bn_ok(s2) and ctx.needs_input_grad[0] and co == ci and kh == 2
-                and _pooled_grad_ok(dy, arg)):
-            # the pool gradient stays pooled: its three consumers expand (dy, arg) while they stage it, and the
-            # bias gradient (the sum of dy) comes out of the block input gradient's epilogue
-            dc, sums, dw2 = _conv2_grad_to_c(dy, out1, c, wd2, s2, bn5, f32, arg=arg)
-            dx = _sconv_run_res_pool(dc, wd1, dy, arg, dbias, co, ci, kh, kh - 1 - 1)
-        else:
-            ds = torch.empty(N, C, H, W, device=dy.device, dtype=x.dtype, memory_format=torch.channels_last)
-            check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C,
-                                          _stream(dy)), "res_tail_bwd")
-            dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
-            dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=ds) if ctx.needs_input_grad[0] else None
-        _, dw1 = _sconv_backward(x, dc, wd1, s1, 1, False)
-        return (dx.to(x_dtype) if dx is not None else None, dw1.to(w1dt), sums[0], None, None, sums[1], sums[2],
-                dw2.to(w2dt), dbias)
-
-
-class ResBlockDown(torch.autograd.Function):
-    """The downsampling residual block with 32 -> 64 channels (SincNet block 2: Residual_block.forward,
-    src/models/DualStreamSEMamba.py:182-200, frozen BN):
-    MaxPool2d((1, 3))(conv2(selu(bn2(conv1(x) + cb))) + conv_downsample(x) + b2 + bd) as one autograd op, so that the
-    max-pool runs without its full-width tensors as in ResBlockIdentity. Forward: conv1 with the BN + SELU epilogue,
-    conv_downsample, then conv2 with the residual sum and the pool in its epilogue (sconv_pool_ok "fwd"; otherwise
-    conv2 and rdx_res_tail_fwd). Backward: the pool gradient stays (dy, argmax byte) for conv2's input and weight
-    gradients and conv_downsample's (sconv_pool_ok "bwd"; otherwise rdx_res_tail_bwd's full-width scatter feeds the
-    plain kernels); the block input's gradient is conv1's input gradient with conv_downsample's added in its
-    epilogue (rdx_sconv_fwd_res), the bits autograd's add of the two produces. The same bits as SConvBnSeluSConv +
-    SConv + ResTail; the two biases' gradient (the sum of dy) is a reduction over the pooled tensor."""
-
-    @staticmethod
-    def forward(ctx, x, w1, conv_bias, mean, invstd, gamma, beta, w2, wdn, bias):
-        _require_gpu(x)
-        x_dtype = x.dtype
-        x = _nhwc(x.to(half_dtype()))
-        co, ci, kh, _ = w1.shape
-        wf1, wd1 = _sconv_w(w1, x.dtype)
-        wf2, wd2 = _sconv_w(w2, x.dtype)
-        wfd, wdd = _sconv_w(wdn, x.dtype)
-        f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
-        N, _, H, W = x.shape
-        out1 = torch.empty(N, co, H + 1, W, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-        c = _sconv_run(x, wf1, ci, co, kh, 1, y2=out1, bn=bn5[:4])
-        co2, ci2, kh2, _ = w2.shape
-        idn = _sconv_run(x, wfd, ci, wdn.shape[0], wdn.shape[2], 0)
+        idn = x if wdn is None else _sconv_run(x, wfd, ci, wdn.shape[0], wdn.shape[2], 0)
         bf = bias.detach().contiguous().float()
         if sconv_pool_ok(w2.shape, W, "fwd") and (N, co2, H + 2 - kh2, W) == tuple(idn.shape):
+            # conv2 with the residual sum and the max-pool in its epilogue: its full-width output is never stored
             y, arg = _sconv_run_pool(out1, wf2, idn, bf, co2)
         else:
-            a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
-            if a.shape != idn.shape:
-                raise ValueError(f"radhip: residual shapes differ {tuple(a.shape)} vs {tuple(idn.shape)}")
-            y = torch.empty(N, co2, H, W // 3, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-            arg = torch.empty(N, co2, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
-            check(_L(a).rdx_res_tail_fwd(_dtype_code(a), _p(a), _p(idn), _p(bf), _p(y), _p(arg), N * H, W, co2,
-                                         _stream(a)), "res_tail_fwd")
+            y, arg = _res_tail_fwd(_sconv_run(out1, wf2, ci2, co2, kh2, 0), idn, bf)
         ctx.save_for_backward(x, wd1, c, out1, wd2, wdd, bn5, arg, *f32)
-        ctx.meta = (tuple(w1.shape), w1.dtype, tuple(w2.shape), w2.dtype, tuple(wdn.shape), wdn.dtype, x_dtype)
+        ctx.meta = (tuple(w1.shape), w1.dtype, tuple(w2.shape), w2.dtype,
+                    None if wdn is None else (tuple(wdn.shape), wdn.dtype), x_dtype)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, wd1, c, out1, wd2, wdd, bn5, arg, *f32 = ctx.saved_tensors
-        s1, w1dt, s2, w2dt, sd, wddt, x_dtype = ctx.meta
+        s1, w1dt, s2, w2dt, down, x_dtype = ctx.meta
         N, _, H, W = x.shape
         C = s2[0]
         dy = _nhwc(dy.to(x.dtype))
         co, ci, kh, _ = s1
-        if (sconv_pool_ok(s2, W, "bwd") and _fused_dgrad_bn_ok(s2) and tuple(sd) == (64, 32, 1, 3)
-                and _pooled_grad_ok(dy, arg)):
+        need_dx = ctx.needs_input_grad[0]
+        pooled = sconv_pool_ok(s2, W, "bwd") and _fused_dgrad_bn_ok(s2) and _pooled_grad_ok(dy, arg)
+        dx = dwd = None
+        if down is None and pooled and need_dx and co == ci and kh == 2:
+            # the pool gradient stays pooled: its three consumers expand (dy, arg) while they stage it, and the
+            # bias gradient (the sum of dy) comes out of the block input gradient's epilogue
+            dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
+            dc, sums, dw2 = _conv2_grad_to_c(dy, out1, c, wd2, s2, bn5, f32, arg=arg)
+            dx = _sconv_run_res_pool(dc, wd1, dy, arg, dbias, co, ci, kh, kh - 1 - 1)
+        elif down is not None and pooled and down[0] == (64, 32, 1, 3):
             dbias = dy.sum((0, 2, 3), dtype=torch.float32)
             dc, sums, dw2 = _conv2_grad_to_c(dy, out1, c, wd2, s2, bn5, f32, arg=arg)
-            dxd = _sconv_dgrad_pool(dy, arg, wdd, sd, W) if ctx.needs_input_grad[0] else None
-            dwd = _sconv_wgrad_pool(x, dy, arg, sd)
+            res = _sconv_dgrad_pool(dy, arg, wdd, down[0], W) if need_dx else None
+            dwd = _sconv_wgrad_pool(x, dy, arg, down[0])
         else:
-            ds = torch.empty(N, C, H, W, device=dy.device, dtype=x.dtype, memory_format=torch.channels_last)
-            dbias = torch.zeros(C, device=dy.device, dtype=torch.float32)
-            check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C,
-                                          _stream(dy)), "res_tail_bwd")
+            ds, dbias = _res_tail_bwd(dy, arg, (N, C, H, W))
             dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
-            dxd, dwd = _sconv_backward(x, ds, wdd, sd, 0, ctx.needs_input_grad[0])
-        dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=dxd) if ctx.needs_input_grad[0] else None
+            res, dwd = (ds, None) if down is None else _sconv_backward(x, ds, wdd, down[0], 0, need_dx)
+        if dx is None and need_dx:
+            # conv1's input gradient + the identity branch's
+            dx = _sconv_run(dc, wd1, co, ci, kh, kh - 1 - 1, res=res)
         _, dw1 = _sconv_backward(x, dc, wd1, s1, 1, False)
         return (dx.to(x_dtype) if dx is not None else None, dw1.to(w1dt), sums[0], None, None, sums[1], sums[2],
-                dw2.to(w2dt), dwd.to(wddt), dbias)
+                dw2.to(w2dt), dbias, dwd.to(down[1]) if down is not None else None)
 
 
 class BnSeluSConv(torch.autograd.Function):
@@ -1254,11 +1261,8 @@ class BnSeluSConv(torch.autograd.Function):
     def forward(ctx, c, conv_bias, mean, invstd, gamma, beta, w2):
         _require_gpu(c)
         c = _nhwc(c.to(half_dtype()))
-        N, C, H, W = c.shape
         f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
-        out1 = torch.empty_like(c)
-        check(_L(c).rdx_bnselu_fwd(_dtype_code(c), _p(c), *[_p(t) for t in f32], _p(out1), N * H * W, C, _stream(c)),
-              "bnselu_fwd")
+        out1 = _bnselu_fwd(c, f32)
         wf2, wd2 = _sconv_w(w2, c.dtype)
         co2, ci2, kh2, _ = w2.shape
         a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
@@ -1285,20 +1289,10 @@ class Block0Front(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, wd, conv_bias, mean, invstd, gamma, beta, w2):
         _require_gpu(x)
-        hd = half_dtype()
-        xb = x.to(hd).contiguous()                                   # one channel: [N, H, W] in memory
-        N, _, H, W = xb.shape
-        C = w1.shape[0]
-        w1b = w1.detach().to(hd).float().reshape(C, 6).contiguous()   # autocast's 16-bit weights
-        wdb = wd.detach().to(hd).float().reshape(C, 3).contiguous()
+        xb, w1b, wdb = _b0_prep(x, w1, wd)
         f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
-        c = torch.empty(N, C, H + 1, W, device=x.device, dtype=hd, memory_format=torch.channels_last)
-        out1 = torch.empty_like(c)
-        idn = torch.empty(N, C, H, W, device=x.device, dtype=hd, memory_format=torch.channels_last)
-        with _timed("sincnet_b0_fwd", x, 2.0 * (xb.numel() + 2 * c.numel() + idn.numel())):
-            check(_L(hd).rdx_sincnet_b0_fwd(_p(xb), _p(w1b), _p(wdb), _p(bn5), _p(c), _p(out1), _p(idn), N, H, W, C,
-                                           _stream(x)), "sincnet_b0_fwd")
-        wf2, wd2 = _sconv_w(w2, hd)
+        c, out1, idn = _b0_fwd(xb, w1b, wdb, bn5)
+        wf2, wd2 = _sconv_w(w2, xb.dtype)
         co2, ci2, kh2, _ = w2.shape
         a = _sconv_run(out1, wf2, ci2, co2, kh2, 0)
         ctx.save_for_backward(xb, w1b, wdb, c, out1, wd2, bn5, *f32)
@@ -1310,19 +1304,12 @@ class Block0Front(torch.autograd.Function):
         xb, w1b, wdb, c, out1, wd2, bn5, *f32 = ctx.saved_tensors
         w1_shape, wd_shape, x_dtype, s2, w2dt = ctx.meta
         N, H, W = xb.shape[0], xb.shape[2], xb.shape[3]
-        C = w1_shape[0]
         da = _nhwc(da.to(xb.dtype))
         dc, sums, dw2 = _conv2_grad_to_c(da, out1, c, wd2, s2, bn5, f32)
-        di = _nhwc(di.to(xb.dtype)) if di is not None else torch.zeros(N, C, H, W, device=xb.device, dtype=xb.dtype,
-                                                                       memory_format=torch.channels_last)
-        dx = torch.empty(N, 1, H, W, device=xb.device, dtype=torch.float32)
-        part = torch.empty(lib().rdx_sincnet_b0_nblk(N * H * W), C * 9, device=xb.device, dtype=torch.float32)
-        with _timed("sincnet_b0_bwd", dc, 2 * (dc.numel() + di.numel()) + 4 * dx.numel() + 2 * xb.numel()):
-            check(_L(xb).rdx_sincnet_b0_bwd(_p(xb), _p(dc), _p(di), _p(w1b), _p(wdb), _p(dx), _p(part), N, H, W, C,
-                                           _stream(dc)), "sincnet_b0_bwd")
-        dw = part.sum(0).view(C, 9)
-        return (dx.to(x_dtype), dw[:, :6].reshape(w1_shape), dw[:, 6:].reshape(wd_shape), sums[0], None, None, sums[1],
-                sums[2], dw2.to(w2dt))
+        di = (_nhwc(di.to(xb.dtype)) if di is not None
+              else torch.zeros(N, w1_shape[0], H, W, device=xb.device, dtype=xb.dtype, memory_format=torch.channels_last))
+        dx, dw1, dwd = _b0_bwd(xb, dc, di, w1b, wdb, (w1_shape, wd_shape))
+        return dx.to(x_dtype), dw1, dwd, sums[0], None, None, sums[1], sums[2], dw2.to(w2dt)
 
 
 class Block0Fused(torch.autograd.Function):
@@ -1336,17 +1323,15 @@ class Block0Fused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, wd, conv_bias, mean, invstd, gamma, beta, w2, b2, bd):
         _require_gpu(x)
-        hd = half_dtype()
-        xb = x.to(hd).contiguous()                                   # one channel: [N, H, W] in memory
+        xb, w1b, wdb = _b0_prep(x, w1, wd)
+        hd = xb.dtype
         N, _, H, W = xb.shape
         C = w1.shape[0]
-        w1b = w1.detach().to(hd).float().reshape(C, 6).contiguous()   # autocast's 16-bit weights
-        wdb = wd.detach().to(hd).float().reshape(C, 3).contiguous()
         f32, bn5 = _bn_rows(conv_bias, mean, invstd, gamma, beta)
         wf2, wd2 = _sconv_w(w2, hd)
         bias = (b2.detach().float() + bd.detach().float()).contiguous()
-        y = torch.empty(N, C, H, W // 3, device=x.device, dtype=hd, memory_format=torch.channels_last)
-        arg = torch.empty(N, C, H, W // 3, device=x.device, dtype=torch.uint8, memory_format=torch.channels_last)
+        y = _empty_nhwc((N, C, H, W // 3), xb)
+        arg = _empty_nhwc((N, C, H, W // 3), xb, torch.uint8)
         # MFMA work: conv2 (32 -> 32, 2 x 3) over N x H x W positions; HBM: x in, y + argmax out
         with _timed("b0x_fwd", x, 2.0 * N * H * W * 32 * 192):
             check(_L(hd).rdx_b0x_fwd(_p(xb), _p(w1b), _p(wdb), _p(bn5), _p(wf2), _p(bias), _p(y), _p(arg), N, H, W,
@@ -1376,25 +1361,11 @@ class Block0Fused(torch.autograd.Function):
             dbias = tot[6432:6464]
             sums = tot[6464:6560].view(3, C)
             return (dx.to(x_dtype), dw1, dwd, sums[0], None, None, sums[1], sums[2], dw2.to(w2dt), dbias, dbias)
-        c = torch.empty(N, C, H + 1, W, device=xb.device, dtype=xb.dtype, memory_format=torch.channels_last)
-        out1 = torch.empty_like(c)
-        idn = torch.empty(N, C, H, W, device=xb.device, dtype=xb.dtype, memory_format=torch.channels_last)
-        check(_L(xb).rdx_sincnet_b0_fwd(_p(xb), _p(w1b), _p(wdb), _p(bn5), _p(c), _p(out1), _p(idn), N, H, W, C,
-                                       _stream(xb)), "sincnet_b0_fwd")
-        dy = _nhwc(dy.to(xb.dtype))
-        ds = torch.empty(N, C, H, W, device=xb.device, dtype=xb.dtype, memory_format=torch.channels_last)
-        dbias = torch.zeros(C, device=xb.device, dtype=torch.float32)
-        check(_L(dy).rdx_res_tail_bwd(_dtype_code(dy), _p(dy), _p(arg), _p(ds), _p(dbias), N * H, W, C, _stream(dy)),
-              "res_tail_bwd")
+        c, out1, _ = _b0_fwd(xb, w1b, wdb, bn5)
+        ds, dbias = _res_tail_bwd(_nhwc(dy.to(xb.dtype)), arg, (N, C, H, W))
         dc, sums, dw2 = _conv2_grad_to_c(ds, out1, c, wd2, s2, bn5, f32)
-        dx = torch.empty(N, 1, H, W, device=xb.device, dtype=torch.float32)
-        part = torch.empty(lib().rdx_sincnet_b0_nblk(N * H * W), C * 9, device=xb.device, dtype=torch.float32)
-        with _timed("sincnet_b0_bwd", dc, 2 * (dc.numel() + ds.numel()) + 4 * dx.numel() + 2 * xb.numel()):
-            check(_L(xb).rdx_sincnet_b0_bwd(_p(xb), _p(dc), _p(ds), _p(w1b), _p(wdb), _p(dx), _p(part), N, H, W, C,
-                                           _stream(dc)), "sincnet_b0_bwd")
-        dw = part.sum(0).view(C, 9)
-        return (dx.to(x_dtype), dw[:, :6].reshape(w1_shape), dw[:, 6:].reshape(wd_shape), sums[0], None, None, sums[1],
-                sums[2], dw2.to(w2dt), dbias, dbias)
+        dx, dw1, dwd = _b0_bwd(xb, dc, ds, w1b, wdb, (w1_shape, wd_shape))
+        return dx.to(x_dtype), dw1, dwd, sums[0], None, None, sums[1], sums[2], dw2.to(w2dt), dbias, dbias
 
 
 # ------------------------------------------------------------ WavLM positional convolution ----

@@ -5,6 +5,7 @@ SincNetEncoder (:206-270), themselves taken from AASIST (models/AASIST.py:325-46
 """
 import os
 import random
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -13,8 +14,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import sinc_x3
-from .ops import (HALF, Block0Convs, Block0Front, Block0Fused, BnSelu, ResBlockIdentity, ResBlockDown, BnSeluSConv, ResTail, SConv, SConvBnSelu, SConvBnSeluSConv, sconv_ok,
-                  sconv_weight_ok, sincconv_absmaxpool)
+from .ops import (HALF, SCONV_CH, SCONV_POOL_DEFAULT, Block0Convs, Block0Front, Block0Fused, BnSelu, BnSeluSConv,
+                  ResBlock, ResTail, SConv, SConvBnSelu, SConvBnSeluSConv, _frozen_invstd, sconv_enabled,
+                  sincconv_absmaxpool)
 
 
 def _half_autocast(x):
@@ -117,97 +119,96 @@ class Residual_block(nn.Module):
         return [] if self.first else list(self.bn1.parameters())
 
     def _fused_ok(self, x):
-        return (x.is_cuda and not self.bn2.training and x.dim() == 4
+        return (x.is_cuda and not self.bn2.training and x.dim() == 4 and x.shape[1] == self.conv1.in_channels
                 and x.is_contiguous(memory_format=torch.channels_last) and self.conv2.out_channels % 8 == 0)
 
     def forward(self, x):
         if not self.first and self.bn1.training:
             with torch.no_grad():
                 self.bn1(x)
-        if self._fused_ok(x):
-            # NHWC fused epilogues (csrc/sincnet.hip): conv1's bias is folded into the frozen-BN+SELU pass,
-            # conv2 / conv_downsample biases into the add + MaxPool2d((1,3)) pass. Under bf16 / fp16 autocast the
-            # 32/64-channel convolutions run on csrc/sconv.hip (conv1 with the BN+SELU in its epilogue).
-            bn = self.bn2
-            bf = _half_autocast(x)
-            invstd = _frozen_invstd(bn)
-            bnp = (self.conv1.bias, bn.running_mean, invstd, bn.weight, bn.bias)
-            w2 = self.conv2.weight
-            # conv1 -> bn2 -> selu -> conv2 as one autograd op on csrc/sconv.hip (its backward reaches conv1's
-            # pre-activation in one pass for the 32-channel blocks)
-            pair = bf and sconv_weight_ok(w2) and os.environ.get("RADHIP_SCONV_PAIR", "1") != "0"
-            idn, a = None, None
-            if (self.first and self.downsample and x.shape[1] == 1 and bf and pair and x.shape[3] >= 3
-                    and self.conv1.out_channels == 32 and os.environ.get("RADHIP_B0X", "1") != "0"):
-                # the whole block in one HIP pass each way (radhip.ops.Block0Fused): no full-size intermediates
-                return Block0Fused.apply(x, self.conv1.weight, self.conv_downsample.weight, *bnp, w2, self.conv2.bias,
-                                         self.conv_downsample.bias)
-            if (self.first and self.downsample and x.shape[1] == 1 and bf
-                    and os.environ.get("RADHIP_FUSED_B0", "1") != "0"):
-                # one input channel: both convolutions (and conv1's BN + SELU) in one HIP pass each way
-                # (radhip.ops.Block0Front; Block0Convs + BnSeluSConv with RADHIP_B0_FWD=0)
-                if pair and os.environ.get("RADHIP_B0_FWD", "1") != "0":
-                    a, idn = Block0Front.apply(x, self.conv1.weight, self.conv_downsample.weight, *bnp, w2)
-                else:
-                    c, idn = Block0Convs.apply(x, self.conv1.weight, self.conv_downsample.weight)
-                    if pair:
-                        a = BnSeluSConv.apply(c, *bnp, w2)
-                    else:
-                        out = BnSelu.apply(c, *bnp)
-            elif bf and sconv_ok(x, self.conv1.weight):
-                if pair and not self.downsample and os.environ.get("RADHIP_RES_FUSED", "1") != "0":
-                    # the whole block as one autograd op: the block input's gradient in one pass
-                    # (conv1's input gradient + the identity branch's, radhip.ops.ResBlockIdentity)
-                    return ResBlockIdentity.apply(x, self.conv1.weight, *bnp, w2, self.conv2.bias)
-                if (pair and self.downsample and sconv_ok(x, self.conv_downsample.weight)
-                        and os.environ.get("RADHIP_RES_FUSED", "1") != "0"
-                        and os.environ.get("RADHIP_SCONV_POOL", "1") != "0"):
-                    # the downsampling block as one autograd op, so that its max-pool needs no full-width tensors
-                    # (radhip.ops.ResBlockDown; RADHIP_SCONV_POOL=0: the three ops below)
-                    return ResBlockDown.apply(x, self.conv1.weight, *bnp, w2, self.conv_downsample.weight,
-                                              self.conv2.bias + self.conv_downsample.bias)
-                if pair:
-                    a = SConvBnSeluSConv.apply(x, self.conv1.weight, 1, *bnp, w2)
-                else:
-                    out = SConvBnSelu.apply(x, self.conv1.weight, 1, *bnp)
-            else:
-                c = F.conv2d(x, self.conv1.weight, None, self.conv1.stride, self.conv1.padding)
+        if not self._fused_ok(x):
+            out = self.conv1(x)
+            out = self.selu(self.bn2(out))
+            out = self.conv2(out)
+            identity = self.conv_downsample(x) if self.downsample else x
+            return self.mp(out + identity)
+        # NHWC fused epilogues (csrc/sincnet.hip): conv1's bias is folded into the frozen-BN+SELU pass, conv2 /
+        # conv_downsample biases into the add + MaxPool2d((1,3)) pass. Under bf16 / fp16 autocast the 32/64-channel
+        # convolutions run on csrc/sconv.hip (conv1 with the BN+SELU in its epilogue). _route names the ops.
+        c1, c2, bn = self.conv1, self.conv2, self.bn2
+        cd = self.conv_downsample if self.downsample else None
+        w1, w2, wd = c1.weight, c2.weight, cd.weight if cd is not None else None
+        bnp = (c1.bias, bn.running_mean, _frozen_invstd(bn), bn.weight, bn.bias)
+        a = c = out = None
+        idn = x
+        for op in _route(self.first, self.downsample, x.shape[1], c1.out_channels, x.shape[3], _half_autocast(x),
+                         _switches()):
+            if op == "Block0Fused":
+                return Block0Fused.apply(x, w1, wd, *bnp, w2, c2.bias, cd.bias)
+            if op == "ResBlock":
+                return ResBlock.apply(x, w1, *bnp, w2, c2.bias + cd.bias if cd is not None else c2.bias, wd)
+            if op == "ResTail":
+                return ResTail.apply(a, idn, c2.bias + cd.bias if cd is not None else c2.bias)
+            if op == "Block0Front":
+                a, idn = Block0Front.apply(x, w1, wd, *bnp, w2)
+            elif op == "Block0Convs":
+                c, idn = Block0Convs.apply(x, w1, wd)
+            elif op == "BnSeluSConv":
+                a = BnSeluSConv.apply(c, *bnp, w2)
+            elif op == "conv1":
+                c = F.conv2d(x, w1, None, c1.stride, c1.padding)
+            elif op == "BnSelu":
                 out = BnSelu.apply(c, *bnp)
-            if a is None:
-                if bf and sconv_ok(out, w2):
-                    a = SConv.apply(out, w2, 0)
-                else:
-                    a = F.conv2d(out, w2, None, self.conv2.stride, self.conv2.padding)
-            if self.downsample:
-                if idn is None and bf and sconv_ok(x, self.conv_downsample.weight):
-                    idn = SConv.apply(x, self.conv_downsample.weight, 0)
-                elif idn is None:
-                    idn = F.conv2d(x, self.conv_downsample.weight, None, self.conv_downsample.stride,
-                                   self.conv_downsample.padding)
-                bias = self.conv2.bias + self.conv_downsample.bias
-            else:
-                idn, bias = x, self.conv2.bias
-            return ResTail.apply(a, idn, bias)
-        out = self.conv1(x)
-        out = self.selu(self.bn2(out))
-        out = self.conv2(out)
-        identity = self.conv_downsample(x) if self.downsample else x
-        return self.mp(out + identity)
+            elif op == "SConvBnSeluSConv":
+                a = SConvBnSeluSConv.apply(x, w1, 1, *bnp, w2)
+            elif op == "SConvBnSelu":
+                out = SConvBnSelu.apply(x, w1, 1, *bnp)
+            elif op == "SConv2":
+                a = SConv.apply(out, w2, 0)
+            elif op == "conv2":
+                a = F.conv2d(out, w2, None, c2.stride, c2.padding)
+            elif op == "SConvDown":
+                idn = SConv.apply(x, wd, 0)
+            elif op == "convDown":
+                idn = F.conv2d(x, wd, None, cd.stride, cd.padding)
+        raise AssertionError("radhip: a residual block's route ends in an op that returns")
 
 
-def _frozen_invstd(bn):
-    """rsqrt(running_var + eps) of a frozen BatchNorm, once per accumulation window (ops.SCONV_WCACHE)."""
-    from . import ops as _ops
-    cache = _ops.SCONV_WCACHE
-    if cache is None:
-        return torch.rsqrt(bn.running_var + bn.eps)
-    key = ("invstd", id(bn.running_var))
-    hit = cache.get(key)
-    if hit is not None and hit[0] is bn.running_var:
-        return hit[1]
-    v = torch.rsqrt(bn.running_var + bn.eps)
-    cache[key] = (bn.running_var, v)
-    return v
+Switches = namedtuple("Switches", "sconv pair b0x fused_b0 b0_fwd res_fused pool")
+
+
+def _switches():
+    """The residual stack's routing switches (RADHIP_<NAME>=0 takes the path the named one replaced); all default
+    to on. RADHIP_SCONV_POOL also takes fwd / bwd (radhip.ops.sconv_pool_ok): only 0 changes the route."""
+    on = lambda name, default="1": os.environ.get(name, default) != "0"
+    return Switches(sconv=sconv_enabled(), pair=on("RADHIP_SCONV_PAIR"), b0x=on("RADHIP_B0X"),
+                    fused_b0=on("RADHIP_FUSED_B0"), b0_fwd=on("RADHIP_B0_FWD"), res_fused=on("RADHIP_RES_FUSED"),
+                    pool=on("RADHIP_SCONV_POOL", SCONV_POOL_DEFAULT))
+
+
+def _route(first, down, ci, co, W, half, sw):
+    """The ops of a fused residual block, in the order Residual_block.forward runs them: first / down: the block's
+    flags, ci -> co its channels, W the input's width, half: 16-bit autocast, sw: _switches(). Names of radhip.ops
+    classes, and conv1 / conv2 / convDown for torch's conv2d, SConv2 / SConvDown for SConv as conv2 / conv_downsample.
+    Every chain ends in an op that produces the block's output."""
+    def sconv(a, b):                       # csrc/sconv.hip has the convolution a -> b channels
+        return half and sw.sconv and a in SCONV_CH and b in SCONV_CH
+    pair = sconv(co, co) and sw.pair       # conv1 -> bn2 -> selu -> conv2 as one autograd op
+    conv2 = ("SConv2" if sconv(co, co) else "conv2",)
+    if first and down and ci == 1 and half:
+        if pair and W >= 3 and co == 32 and sw.b0x:
+            return ("Block0Fused",)        # the whole block in one HIP pass each way
+        if sw.fused_b0:                    # one input channel: conv1 and conv_downsample in one HIP pass each way
+            if pair and sw.b0_fwd:
+                return ("Block0Front", "ResTail")
+            return ("Block0Convs",) + (("BnSeluSConv",) if pair else ("BnSelu",) + conv2) + ("ResTail",)
+    if sconv(ci, co):
+        if pair and sw.res_fused and (sw.pool or not down):
+            return ("ResBlock",)           # the whole block as one autograd op (RADHIP_SCONV_POOL=0: not block 2)
+        front = ("SConvBnSeluSConv",) if pair else ("SConvBnSelu",) + conv2
+    else:
+        front = ("conv1", "BnSelu") + conv2
+    return front + (("SConvDown" if sconv(ci, co) else "convDown",) if down else ()) + ("ResTail",)
 
 
 class SincNetEncoder(nn.Module):

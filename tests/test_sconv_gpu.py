@@ -145,7 +145,7 @@ def test_bnselu_sconv_block0_matches_unfused():
 
 @pytest.mark.parametrize("C,W", [(32, 7163), (64, 795), (32, 301)])
 def test_res_block_identity_matches_autograd_sum(C, W, monkeypatch):
-    """A non-downsampling Residual_block as one op (radhip.ops.ResBlockIdentity: the block input's gradient = conv1's
+    """A non-downsampling Residual_block as one op (radhip.ops.ResBlock: the block input's gradient = conv1's
     input gradient + the identity branch's, added in the input-gradient kernel's epilogue) against the same block
     with autograd summing the two branches (RADHIP_RES_FUSED=0): the same kernels and the same bf16 add, so the
     output, the input gradient and the weight gradients are bit-identical (the bias / BN channel sums come from fp32

@@ -249,7 +249,7 @@ TAILS = {"res_tail_fwd", "res_tail_bwd"}
 @pytest.mark.parametrize("switch", ["1", "fwd", "bwd"])
 @pytest.mark.parametrize("filts", [[32, 32], [64, 64], [32, 64]])
 def test_residual_block_same_with_and_without_the_pooled_path(dtype, switch, filts, monkeypatch):
-    """Residual_block under autocast (ResBlockIdentity; ResBlockDown for the downsampling block 2) with
+    """Residual_block under autocast (radhip.ops.ResBlock, with the downsample weight for block 2) with
     RADHIP_SCONV_POOL = 1 / fwd / bwd against 0: the same output and gradients, bit for bit except the fp32 channel
     sums; and the launches really are the pooled ones (no tail kernel on the half that is switched on)."""
     import radhip.ops as ops
