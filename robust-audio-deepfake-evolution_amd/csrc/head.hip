@@ -248,7 +248,8 @@ __global__ __launch_bounds__(256) void se_wgrad_kernel(const float* __restrict__
 
 
 // ---- Attention pooling of the head (src/models/DualStreamSEMamba.py:700-770, Model.forward's tail) under autocast:
-//   z = round(f w^T + b) [B, T] (attention_pool, a 1-output linear), a = softmax_t(z) in fp32, a16 = round(a),
+//   z = round(f w^T + b) [B, T] (attention_pool, a 1-output linear), a = softmax_t(z) in fp32 (evaluated in fp64 and
+//   rounded once to fp32), a16 = round(a),
 //   feat = round(a16^T f) [B, C] (autocast's bmm on the 16-bit attention weights).
 // One workgroup per utterance, f [T, C] read twice (scores, then the weighted sum). Backward from dfeat [B, C]:
 //   da = round(f dfeat) [T], df1 = round(a16 dfeat^T); dz = round(a (da - sum_t a da)) (softmax backward in fp32 on the
@@ -273,6 +274,17 @@ __device__ __forceinline__ float ap_block_sum(float v, float* red) {
   if (lane == 0) red[w] = v;
   __syncthreads();
   float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < AP_T / 64; ++i) s += red[i];
+  return s;
+}
+__device__ __forceinline__ double ap_block_sum_d(double v, double* red) {   // red: AP_T / 64 doubles, 8-byte aligned
+  v = wave_sum_d(v);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
 #pragma unroll
   for (int i = 0; i < AP_T / 64; ++i) s += red[i];
   return s;
@@ -357,17 +369,16 @@ __global__ __launch_bounds__(AP_T) void attn_pool_fwd_kernel(ApArgs a) {
   float mx = -INFINITY;
   for (int t = threadIdx.x; t < T; t += AP_T) mx = fmaxf(mx, sz[t]);
   mx = ap_block_max(mx, red);
-  float sum = 0.f;
-  for (int t = threadIdx.x; t < T; t += AP_T) {
-    const float e = __expf(sz[t] - mx);
-    sz[t] = e;
-    sum += e;
-  }
-  sum = ap_block_sum(sum, red);
-  const float inv = 1.0f / sum;
+  // the softmax's exponentials and their sum in fp64 (at most 4 rows a thread, each exponential taken twice), a
+  // rounded to fp32 once at the end: a, and so a16 = round(a), then does not depend on the order of the sum or on
+  // __expf's last bits, which an fp32 evaluation carries into a16 wherever a lies within a few fp32 ulps of a 16-bit
+  // rounding boundary (an a16 one ulp off moves df1 in every channel of its row)
+  double sum = 0.0;
+  for (int t = threadIdx.x; t < T; t += AP_T) sum += exp((double)sz[t] - (double)mx);
+  sum = ap_block_sum_d(sum, reinterpret_cast<double*>(red));
   __syncthreads();
   for (int t = threadIdx.x; t < T; t += AP_T) {
-    const float av = sz[t] * inv;
+    const float av = (float)(exp((double)sz[t] - (double)mx) / sum);
     a.a[(int64_t)b * T + t] = av;
     sz[t] = hround(av);
   }
