@@ -252,6 +252,32 @@ int rdx_focal_mixup_fwd(const void* logits, int logits_bf16, int ld, int B, int 
                         int mode, float scale, float* loss, float* dlogits, void* stream);
 int rdx_focal_mixup_bwd(const float* grad, const float* dlogits, void* out, int out_bf16, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixup OC-Softmax + supervised-contrastive criteria over the features (src/loss.py:5-152 as train_epoch combines
+ * them, src/main.py:1054-1071), csrc/ocsupcon.hip. Per micro-batch k of B = rows_per_lam rows (K = R / B of them),
+ * with z = normalize(f), w = normalize(center) (eps 1e-12), lam_k = lam[k] (1 when lam is NULL):
+ *   L_k = lam_k (P(ya) + lambda_supcon S(ya)) + (1 - lam_k) (P(yb) + lambda_supcon S(yb))     (yb NULL: the ya term)
+ *   P(y) = mean_i softplus(alpha (y_i == 1 ? r_real - z_i.w : z_i.w - r_fake))               (center NULL: P = 0)
+ *   S(y) = SupCon(z, y) at `temperature` / `base_temperature`, one view, mode 'all'          (lambda_supcon 0: off)
+ *   loss = scale * sum_k L_k
+ * feats [R, D] (row stride ld, unit column stride; the library's 16-bit type when feats_bf16 else fp32), center
+ * fp32 [D], ya / yb int64 [R]. Outputs, all fp32: loss (scalar), dfeats [R, D] = d loss / d feats, dcenter_parts
+ * [K, D] = each micro-batch's d loss / d center (with a center), loss_parts [K] workspace (K > 1). One workgroup per
+ * micro-batch, every reduction in a fixed order: the same inputs give the same bits.
+ * rdx_ocsupcon_eligible states the supported shapes: 2 <= B <= 64, 1 <= D <= 256, R % B == 0, ld >= D, feats
+ * 16-byte aligned; outside them rdx_ocsupcon_mixup_fwd returns RDX_EUNSUPPORTED.
+ * rdx_ocsupcon_mixup_bwd: out[n = R*D] = grad[0] * dfeats in the features' dtype, and (dcenter_parts given)
+ * dcenter[D] = grad[0] * sum_k dcenter_parts[k] added in the order k = 0 .. K-1.
+ * ------------------------------------------------------------------------------------------ */
+int rdx_ocsupcon_eligible(const void* feats, int ld, int R, int D, int B);
+int rdx_ocsupcon_mixup_fwd(const void* feats, int feats_bf16, int ld, int R, int D, const float* center,
+                           const int64_t* ya, const int64_t* yb, const float* lam, int rows_per_lam,
+                           float r_real, float r_fake, float alpha, float lambda_supcon, float temperature,
+                           float base_temperature, float scale, float* loss, float* loss_parts, float* dfeats,
+                           float* dcenter_parts, void* stream);
+int rdx_ocsupcon_mixup_bwd(const float* grad, const float* dfeats, void* out, int out_bf16, int64_t n,
+                           const float* dcenter_parts, int K, int D, float* dcenter, void* stream);
+
 /* ---- SincNet residual stack, NHWC fused epilogues (Residual_block.forward,
  * src/models/DualStreamSEMamba.py:182-200, with freeze_bn: src/main.py:44-51,1016-1018) -----------
  * Activations are [npix, C] row-major (channels_last), C % 8 == 0, C <= 512, 256 % (C/8) == 0.

@@ -28,7 +28,11 @@ Differences, all documented in DESIGN.md:
     (the reference's strict=False silently drops mismatched keys); tensorboard scalars are not written;
   * --save_train_state additionally writes weights/train_state_epoch_XXX.pt (last 2 kept) after every
     epoch: weights, optimizer, scheduler, scaler, EMA, SWA, best metrics, loader generator, host/device
-    RNG states; --resume on such a file continues the run where it stopped.
+    RNG states; --resume on such a file continues the run where it stopped;
+  * "loss": "OCSoftmax": the reference saves the model alone, so its learnt centre is lost. Every weights/*.pth
+    written here stays a plain model state dict and gets a sibling weights/<stem>.criterion.pt holding the
+    criterion's state; --eval, --eval_model_weights, --pretrained_weights and --resume load the sibling when it
+    exists and otherwise say loudly that the centre is freshly drawn (the reference's behaviour).
 """
 import argparse
 import json
@@ -88,6 +92,52 @@ def protocol_paths(config, track, database_path):
     trn = (Path(config["data_config"]["custom_train_protocol"])
            if "custom_train_protocol" in config.get("data_config", {}) else proto / "{}.cm.train.trn.txt".format(p))
     return trn, proto / "{}.cm.dev.trl.txt".format(p), proto / "{}.cm.eval.trl.txt".format(p)
+
+
+def criterion_sibling(path):
+    """weights/<stem>.pth -> weights/<stem>.criterion.pt: where a criterion with parameters (OC-Softmax's centre)
+    is kept. The .pth files stay plain model state dicts, loadable by the reference, which saves the model only
+    (its --eval then scores against a freshly drawn centre)."""
+    path = Path(path)
+    return path.with_name(path.stem + ".criterion.pt")
+
+
+def criterion_has_state(criterion):
+    return isinstance(criterion, torch.nn.Module) and any(True for _ in criterion.parameters())
+
+
+def save_weights(state, path, criterion=None):
+    """torch.save(state, path) and, when the criterion has parameters, its state dict beside it."""
+    torch.save(state, path)
+    if criterion_has_state(criterion):
+        torch.save({k: v.detach().cpu().clone() for k, v in criterion.state_dict().items()}, criterion_sibling(path))
+
+
+def remove_weights(path):
+    Path(path).unlink(missing_ok=True)
+    criterion_sibling(path).unlink(missing_ok=True)
+
+
+def load_criterion(criterion, path, log=print):
+    """Load <stem>.criterion.pt beside the weights file `path` into the criterion, in place. Without the file the
+    criterion keeps its freshly drawn parameters (the reference's behaviour) and one loud line says so. Returns
+    whether the file was loaded."""
+    if not criterion_has_state(criterion):
+        return False
+    sib = criterion_sibling(path)
+    if not sib.exists():
+        log(f"WARNING: no {sib.name} beside {path}: the OC-Softmax CENTRE IS FRESHLY DRAWN (the reference's "
+            "behaviour); scores against it do not belong to these weights")
+        return False
+    sd = torch.load(sib, map_location="cpu", weights_only=True)
+    own = criterion.state_dict()
+    if set(sd) != set(own):
+        raise ValueError(f"{sib}: criterion state has keys {sorted(sd)}, expected {sorted(own)}")
+    with torch.no_grad():       # in place: captured graphs read the centre through its pointer
+        for k, v in own.items():
+            v.copy_(sd[k])
+    log(f"Criterion state loaded : {sib}")
+    return True
 
 
 class SWA:
@@ -217,6 +267,7 @@ class Runner:
         model_path = args.eval_model_weights if args.eval_model_weights is not None else config["model_path"]
         load_weights(model, model_path, self.device, strict=True)
         self.log("Model loaded : {}".format(model_path))
+        load_criterion(self.criterion, model_path, self.log)
         self.log("Start evaluation...")
         if config.get("is_eval_2021", False):
             trial = self.database_path / "ASVspoof2021.DF.cm.eval.trl.txt"
@@ -326,6 +377,9 @@ class Runner:
         args, config = self.args, self.config
         model = self.build_model()
         self.criterion = build_criterion(config, self.device)
+        for given in (args.pretrained_weights, args.resume):      # (a full train state carries the criterion itself)
+            if given and not (given == args.resume and self.resume_state is not None):
+                load_criterion(self.criterion, given, self.log)
         if args.eval:
             self.run_eval(model)
             return
@@ -361,7 +415,7 @@ class Runner:
         trainer = Trainer(model, config, self.device, total, self.amp, world_group=None, criterion=self.criterion)
         self.log(f"[Schedule] micro-batches/epoch={len(feeder)}, accumulation_steps={accum} -> "
                  f"optimizer_steps/epoch={steps_per_epoch}, total_steps={total}")
-        swa = SWA(trainer.params)
+        swa = SWA(trainer.model_params)     # model tensors only: the reference's SWA and EMA never hold the centre
         best = {"dev_eer": 100.0, "eval_eer": 100.0, "dev_tdcf": 100.0, "eval_tdcf": 100.0}
         start = args.start_epoch
         # graph capture consumes host RNG draws and runs warm-up passes, so it happens before a full
@@ -398,8 +452,8 @@ class Runner:
                 if self.rank == 0:
                     for old in self.weights_dir.glob("epoch_*_*.pth"):
                         if old.name != name:
-                            old.unlink(missing_ok=True)
-                    torch.save(model.state_dict(), self.weights_dir / name)
+                            remove_weights(old)
+                    save_weights(model.state_dict(), self.weights_dir / name, self.criterion)
                 if str_to_bool(config["eval_all_best"]):
                     self.score(model, file_eval, eval_base, self.eval_score_path, eval_trial)
                     eval_eer, eval_tdcf = self.tdcf(self.eval_score_path,
@@ -412,7 +466,7 @@ class Runner:
                         log_text += "best tdcf, {:.4f}".format(eval_tdcf)
                         best["eval_tdcf"] = eval_tdcf
                         if self.rank == 0:
-                            torch.save(model.state_dict(), self.weights_dir / "best.pth")
+                            save_weights(model.state_dict(), self.weights_dir / "best.pth", self.criterion)
                     self.log(log_text)
                     if self.rank == 0:
                         with open(self.tag / "metric_log.txt", "a") as f_log:
@@ -424,10 +478,10 @@ class Runner:
                 swa.update()
             if ((epoch + 1) % 10 == 0 or epoch == config["num_epochs"] - 1) and self.rank == 0:
                 ck = self.weights_dir / "checkpoint_epoch_{:03d}.pth".format(epoch)
-                torch.save(model.state_dict(), ck)
+                save_weights(model.state_dict(), ck, self.criterion)
                 cks = sorted(self.weights_dir.glob("checkpoint_epoch_*.pth"), key=lambda x: int(x.stem.split("_")[-1]))
                 for old in cks[:-3]:
-                    old.unlink(missing_ok=True)
+                    remove_weights(old)
             if args.save_train_state and self.rank == 0:
                 self.save_train_state(self.weights_dir / "train_state_epoch_{:03d}.pt".format(epoch), epoch, model,
                                       trainer, swa, feeder, best)
@@ -457,13 +511,13 @@ class Runner:
             with open(self.tag / "metric_log.txt", "a") as f_log:
                 f_log.write("=" * 5 + "\n")
                 f_log.write("EER: {:.3f}, min t-DCF: {:.5f}".format(eval_eer, eval_tdcf))
-            torch.save(model.state_dict(), self.weights_dir / "swa.pth")
+            save_weights(model.state_dict(), self.weights_dir / "swa.pth", self.criterion)
         if eval_eer <= best["eval_eer"]:
             best["eval_eer"] = eval_eer
         if eval_tdcf <= best["eval_tdcf"]:
             best["eval_tdcf"] = eval_tdcf
             if self.rank == 0:
-                torch.save(final_state, self.weights_dir / "best.pth")
+                save_weights(final_state, self.weights_dir / "best.pth", self.criterion)
         self.log("Exp FIN. EER: {:.3f}, min t-DCF: {:.5f}".format(best["eval_eer"], best["eval_tdcf"]))
         if config.get("auto_eval_2021_df", False):
             self.auto_eval_2021(model)
@@ -490,6 +544,7 @@ class Runner:
                 return
             best = eps[-1]
         load_weights(model, best, self.device, strict=True)
+        load_criterion(self.criterion, best, self.log)
         keys = genSpoof_list(trial, is_train=False, is_eval=True, is_2021=True)
         out = self.tag / "eval_scores_2021DF.txt"
         self.score(model, keys, Path(root), out, trial, fmt="2021", zero_on_error=True)

@@ -215,6 +215,11 @@ class Model(nn.Module):
         # set by radhip/window.py for an adversarial pass: its SincNet output (a leaf), from one batched pass
         self.sinc_given = None
 
+    def logit_only_parameters(self):
+        """Parameters that only the logits depend on: a criterion that reads the features alone (OC-Softmax) leaves
+        them without a gradient (radhip.train.Trainer)."""
+        return list(self.classifier.parameters())
+
     @staticmethod
     def sinc_side_stream(x):
         """The stream the SincNet branch runs on (None: in order on the current stream). radhip/window.py puts

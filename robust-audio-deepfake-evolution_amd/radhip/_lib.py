@@ -206,6 +206,10 @@ SIGNATURES = {
     "rdx_focal_mixup_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_int,
                                     c_f32, c_vp, c_vp, c_vp]),
     "rdx_focal_mixup_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "rdx_ocsupcon_eligible": (c_int, [c_vp, c_int, c_int, c_int, c_int]),
+    "rdx_ocsupcon_mixup_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int] + [c_f32] * 7
+                               + [c_vp] * 5),
+    "rdx_ocsupcon_mixup_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp, c_vp]),
     "rdx_hgemm_x3": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int,
                              c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rdx_hgemm_batched": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int,

@@ -554,6 +554,92 @@ def mixup_focal(logits, ya, yb, lam, rows_per_lam, focal, divisor):
     return MixupFocal.apply(logits, ya, yb, lam, rows_per_lam, alpha, float(focal.gamma), mode, scale)
 
 
+def ocsupcon_eligible(feats, rows_per_lam, center=None):
+    """True when csrc/ocsupcon.hip takes these features (and centre): a [R, D] bf16 / fp16 / fp32 device tensor with
+    unit column stride and the shape limits the library states (rdx_ocsupcon_eligible: 2 <= B <= 64, D <= 256,
+    R % B == 0, 16-byte-aligned base), the centre a contiguous fp32 device tensor of D elements. Callers take the
+    module path (radhip.train.OCSoftmax / SupConLoss) otherwise."""
+    if not (torch.is_tensor(feats) and feats.is_cuda and feats.dim() == 2 and feats.dtype in (*HALF, torch.float32)
+            and feats.stride(1) == 1 and feats.shape[0] > 0):
+        return False
+    if center is not None and not (center.is_cuda and center.dtype == torch.float32 and center.is_contiguous()
+                                   and center.numel() == feats.shape[1]):
+        return False
+    return bool(_L(feats).rdx_ocsupcon_eligible(_p(feats), feats.stride(0), feats.shape[0], feats.shape[1],
+                                                int(rows_per_lam)))
+
+
+class MixupOcSupcon(torch.autograd.Function):
+    """scale * sum_k [lam_k L_k(ya) + (1 - lam_k) L_k(yb)], L = OC-Softmax(feats, center) + lambda * SupCon(feats),
+    on csrc/ocsupcon.hip: the value, d/dfeats and each micro-batch's d/dcenter in one launch, the backward in one
+    more (lam_k = lam[k], a device tensor; micro-batch k = rows [k * rows_per_lam, (k + 1) * rows_per_lam)).
+    center None: SupCon alone. The centre is read through its own storage (no copy), so a captured launch sees
+    every later optimizer update. Shapes outside ocsupcon_eligible raise (the C entry's RDX_EUNSUPPORTED)."""
+
+    @staticmethod
+    def forward(ctx, feats, center, ya, yb, lam, rows_per_lam, r_real, r_fake, alpha, lambda_supcon, temperature,
+                base_temperature, scale):
+        _require_gpu(feats, ya)
+        if feats.dim() != 2 or feats.dtype not in (*HALF, torch.float32) or feats.stride(1) != 1:
+            raise ValueError("mixup ocsupcon: [R, D] bf16/fp16/fp32 features with unit column stride required")
+        R, D = feats.shape
+        B = int(rows_per_lam)
+        if center is not None and not (center.is_cuda and center.dtype == torch.float32 and center.is_contiguous()
+                                       and center.numel() == D):
+            raise ValueError("mixup ocsupcon: the centre must be a contiguous fp32 device tensor of D elements")
+        ya = ya.contiguous()
+        yb = yb.contiguous() if yb is not None else None
+        lam = lam.contiguous().float() if lam is not None else None
+        if ya.dtype != torch.int64 or ya.numel() != R or (yb is not None and (yb.dtype != torch.int64 or yb.numel() != R)):
+            raise ValueError("mixup ocsupcon: int64 labels of R entries required")
+        if lam is not None and B > 0 and lam.numel() * B < R:
+            raise ValueError("mixup ocsupcon: lam has too few entries for the rows")
+        K = R // B if B > 0 and R % B == 0 else 1
+        dev = feats.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        parts = torch.empty(K, device=dev, dtype=torch.float32) if K > 1 else None
+        d32 = torch.empty(R, D, device=dev, dtype=torch.float32)
+        dcp = torch.empty(K, D, device=dev, dtype=torch.float32) if center is not None else None
+        check(_L(feats).rdx_ocsupcon_mixup_fwd(
+            _p(feats), int(feats.dtype in HALF), feats.stride(0), R, D, _p(center) if center is not None else None,
+            _p(ya), _p(yb) if yb is not None else None, _p(lam) if lam is not None else None, B, float(r_real),
+            float(r_fake), float(alpha), float(lambda_supcon), float(temperature), float(base_temperature),
+            float(scale), _p(loss), _p(parts) if parts is not None else None, _p(d32),
+            _p(dcp) if dcp is not None else None, _stream(feats)), "ocsupcon_mixup_fwd")
+        ctx.save_for_backward(d32, dcp)
+        ctx.out_dtype = feats.dtype
+        ctx.center_shape = center.shape if center is not None else None
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d32, dcp = ctx.saved_tensors
+        g = g.float().contiguous()
+        out = torch.empty(d32.shape, device=d32.device, dtype=ctx.out_dtype)
+        dc = torch.empty(ctx.center_shape, device=d32.device, dtype=torch.float32) if dcp is not None else None
+        check(_L(ctx.out_dtype).rdx_ocsupcon_mixup_bwd(
+            _p(g), _p(d32), _p(out), int(ctx.out_dtype in HALF), d32.numel(), _p(dcp) if dcp is not None else None,
+            dcp.shape[0] if dcp is not None else 0, d32.shape[1], _p(dc) if dc is not None else None, _stream(d32)),
+            "ocsupcon_mixup_bwd")
+        return (out, dc) + (None,) * 11
+
+
+def mixup_ocsupcon(feats, ya, yb, lam, rows_per_lam, oc, supcon, lambda_supcon, divisor):
+    """The feature-side criteria of a pass, divided by `divisor` (the accumulation steps): `oc` a
+    radhip.train.OCSoftmax or None, `supcon` a radhip.train.SupConLoss or None (then lambda_supcon is ignored); each
+    micro-batch of rows_per_lam rows is averaged over its rows."""
+    if oc is None and supcon is None:
+        raise ValueError("mixup ocsupcon: neither OC-Softmax nor SupCon given")
+    lsc = float(lambda_supcon) if supcon is not None else 0.0
+    if oc is None and lsc == 0.0:
+        return feats.float().sum() * 0.0        # SupCon alone at weight 0: no criterion left to launch
+    return MixupOcSupcon.apply(feats, oc.center if oc is not None else None, ya, yb, lam, rows_per_lam,
+                               oc.r_real if oc is not None else 0.0, oc.r_fake if oc is not None else 0.0,
+                               oc.alpha if oc is not None else 0.0, lsc,
+                               supcon.temperature if supcon is not None else 1.0,
+                               supcon.base_temperature if supcon is not None else 1.0, 1.0 / divisor)
+
+
 # --------------------------------------------------------------------------- multi-tensor cast ----
 def cast_many(srcs, dsts):
     """dsts[k] = srcs[k] rounded to the dsts' 16-bit dtype (bf16 or fp16), fp32 contiguous sources, one launch per

@@ -63,9 +63,118 @@ class FocalLoss(nn.Module):
         return per_utt.mean()
 
 
-def build_criterion(config, device):
-    """Loss selection of main.py:270-312 (focal when loss == 'Focal' or use_focal_loss, else weighted CE)."""
+class OCSoftmax(nn.Module):
+    """One-class softmax on the embedding (src/loss.py:5-47): with w = normalize(center), s = normalize(x) . w,
+        loss = mean_i softplus(alpha * (y_i == 1 ? r_real - s_i : s_i - r_fake))
+    (torch's softplus: x itself above 20, so no overflow). `center` is a learnable [1, feat_dim] parameter drawn as
+    the reference draws it: randn(1, feat_dim), then kaiming_uniform_(center, 0.25), both on the global CPU
+    generator. Arithmetic runs in the centre's dtype (fp32; fp64 after .double()), also under autocast.
+    Scoring uses s (radhip.infer._scores, src/main.py:978-982)."""
+
+    def __init__(self, feat_dim=2, r_real=0.9, r_fake=0.5, alpha=20.0):
+        super().__init__()
+        self.feat_dim, self.r_real, self.r_fake, self.alpha = feat_dim, r_real, r_fake, alpha
+        self.center = nn.Parameter(torch.randn(1, feat_dim))
+        nn.init.kaiming_uniform_(self.center, 0.25)
+
+    def scores(self, x):
+        w = F.normalize(self.center, p=2, dim=1)
+        return (F.normalize(x.to(w.dtype), p=2, dim=1) * w).sum(1)
+
+    def forward(self, x, labels):
+        s = self.scores(x)
+        return F.softplus(self.alpha * torch.where(labels == 1, self.r_real - s, s - self.r_fake)).mean()
+
+
+class SupConLoss(nn.Module):
+    """Supervised contrastive loss (src/loss.py:49-152) as the reference calls it: one view, mode 'all', on rows
+    z that are already L2-normalised. l = z z^T / T minus its row maximum (a constant); the diagonal leaves both
+    the positives and the denominator; log_prob = l - log(sum_{j != i} exp(l_ij) + 1e-8); row loss
+    -(T / T_base) * sum_pos log_prob / max(n_pos, 1e-8) (a row without a positive gives 0; a non-finite row is
+    set to 0); mean over the rows. fp32 (fp64 for fp64 rows), also under autocast."""
+
+    def __init__(self, temperature=0.07, base_temperature=0.07):
+        super().__init__()
+        self.temperature, self.base_temperature = temperature, base_temperature
+
+    def forward(self, z, labels):
+        z = z if z.dtype == torch.float64 else z.float()
+        n = z.shape[0]
+        with torch.autocast(z.device.type, enabled=False):
+            logits = torch.matmul(z, z.t()) / self.temperature
+        logits = logits - logits.max(dim=1, keepdim=True)[0].detach()
+        off = ~torch.eye(n, dtype=torch.bool, device=z.device)
+        labels = labels.reshape(-1, 1)
+        pos = ((labels == labels.t()) & off).to(z.dtype)
+        log_prob = logits - torch.log((torch.exp(logits) * off).sum(1, keepdim=True) + 1e-8)
+        row = -(self.temperature / self.base_temperature) * (pos * log_prob).sum(1) / pos.sum(1).clamp(min=1e-8)
+        return torch.where(torch.isfinite(row), row, torch.zeros_like(row)).mean()
+
+
+def oc_feat_dim(model_config):
+    """The OC-Softmax feature width the reference infers from the architecture name (src/main.py:279-288)."""
+    arch = model_config.get("architecture", "")
+    dim = 160
+    if "CascadeMamba" in arch:
+        dim = 128
+    if any(a in arch for a in ("WavLMMamba", "MoEMambaASV", "DualStreamSEMamba")):
+        dim = model_config.get("emb_size", 144)
+    return dim
+
+
+def build_supcon(config):
+    """(SupConLoss(0.07), lambda) or (None, 0.0). As the reference reads them: use_supcon at the top level OR in
+    training_config (src/main.py:182); lambda_supcon at the TOP level only, default 0.1 (src/main.py:1020: a
+    training_config["lambda_supcon"], which the shipped configs carry, is never read)."""
     tc = config.get("training_config", {})
+    if config.get("use_supcon", False) or tc.get("use_supcon", False):
+        return SupConLoss(temperature=0.07), float(config.get("lambda_supcon", 0.1))
+    return None, 0.0
+
+
+def criterion_loss(criterion, supcon, lambda_supcon, out, feats, target):
+    """compute_loss of train_epoch (src/main.py:1054-1064): OC-Softmax on the features or focal / CE on the logits,
+    plus lambda * SupCon(normalize(feats))."""
+    loss = criterion(feats, target) if isinstance(criterion, OCSoftmax) else criterion(out, target)
+    if supcon is not None:
+        z = F.normalize(feats if feats.dtype == torch.float64 else feats.float(), dim=1)
+        loss = loss + lambda_supcon * supcon(z, target)
+    return loss
+
+
+def feats_loss(criterion, supcon, lambda_supcon, accum, feats, ya, yb, lam, B, fused=True):
+    """The feature-side criteria of a pass over feats [K * B, D], micro-batch k mixed with lam[k], divided by
+    `accum`: lam (P(ya) + lambda S(ya)) + (1 - lam) (P(yb) + lambda S(yb)) with P = OC-Softmax (when `criterion` is
+    one) and S = SupCon (when given); yb None: the ya term alone, lam None: 1. One HIP launch forward and one
+    backward (ops.mixup_ocsupcon, csrc/ocsupcon.hip) where the kernel takes the shape (ops.ocsupcon_eligible), the
+    modules otherwise (and on the CPU, and with fused=False)."""
+    oc = criterion if isinstance(criterion, OCSoftmax) else None
+    lam = lam.reshape(-1) if lam is not None else None
+    if fused and ops.ocsupcon_eligible(feats, B, oc.center if oc is not None else None):
+        return ops.mixup_ocsupcon(feats, ya, yb, lam, B, oc, supcon, lambda_supcon, accum)
+    tot = 0.0
+    for k in range(feats.shape[0] // B):
+        sl = slice(k * B, (k + 1) * B)
+        f = feats[sl]
+        z = F.normalize(f if f.dtype == torch.float64 else f.float(), dim=1) if supcon is not None else None
+
+        def one(y):
+            v = oc(f, y) if oc is not None else 0.0
+            return v + lambda_supcon * supcon(z, y) if supcon is not None else v
+        l1 = lam[k] if lam is not None else 1.0
+        tot = tot + l1 * one(ya[sl])
+        if yb is not None:
+            tot = tot + (1.0 - l1) * one(yb[sl])
+    return tot / accum
+
+
+def build_criterion(config, device):
+    """Loss selection of main.py:270-312 (OC-Softmax when loss == 'OCSoftmax'; focal when loss == 'Focal' or
+    use_focal_loss, else weighted CE). OC-Softmax draws its centre here, from the global torch generator."""
+    tc = config.get("training_config", {})
+    if config.get("loss") == "OCSoftmax":
+        return OCSoftmax(oc_feat_dim(config.get("model_config", {})), tc.get("ocsoftmax_r_real", 0.9),
+                         tc.get("ocsoftmax_r_fake", 0.5), tc.get("ocsoftmax_alpha", 20.0)).to(device)
     if config.get("loss") == "Focal" or tc.get("use_focal_loss", False):
         return FocalLoss(tc.get("focal_alpha", 0.25), tc.get("focal_gamma", 2.0),
                          tc.get("focal_alpha_mode", "per_class"))
@@ -211,8 +320,12 @@ class FlatGrads:
     """Every trainable tensor's .grad is a view into one contiguous fp32 buffer: zero_grad is one
     memset, clipping one norm, and a data-parallel step one all-reduce (11.9 MB for Phase 6)."""
 
-    def __init__(self, params):
+    def __init__(self, params, unclipped=()):
+        """unclipped: trainable tensors that share the buffer (zero_grad, all-reduce) but stay out of clip_norm_
+        (the criterion's: the reference clips model.parameters() only, src/main.py:1104); they sit at the end."""
         self.params = [p for p in params if p.requires_grad]
+        n_clip = sum(p.numel() for p in self.params)
+        self.params += [p for p in unclipped if p.requires_grad]
         total = sum(p.numel() for p in self.params)
         dev = self.params[0].device
         self.flat = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -224,6 +337,7 @@ class FlatGrads:
             p.grad = self.flat[off:off + n].view_as(p)
             self._ptrs.append(p.grad.data_ptr())
             off += n
+        self.clipped = self.flat if n_clip == total else self.flat[:n_clip]
 
     def bound(self):
         """True while every parameter's .grad is still its view of the flat buffer."""
@@ -233,8 +347,8 @@ class FlatGrads:
         """torch.nn.utils.clip_grad_norm_ over the parameters (error_if_nonfinite off) on the flat buffer: the total
         2-norm in one reduction and min(1, max_norm / (norm + 1e-6)) applied in one multiply, instead of a norm per
         tensor (torch's multi-tensor kernels deal 64 K elements per block: ~0.1 ms per step for these ~3 M)."""
-        norm = torch.linalg.vector_norm(self.flat, 2)
-        self.flat.mul_(torch.clamp(max_norm / (norm + 1e-6), max=1.0))
+        norm = torch.linalg.vector_norm(self.clipped, 2)
+        self.clipped.mul_(torch.clamp(max_norm / (norm + 1e-6), max=1.0))
         return norm
 
     def zero(self):
@@ -416,6 +530,10 @@ class Trainer:
         self.freeze_bn = bool(tc.get("freeze_bn", False))
         self.amp_dtype = amp_dtype
         self.criterion = criterion if criterion is not None else build_criterion(config, device)
+        self.supcon, self.lambda_supcon = build_supcon(config)
+        # the criterion's own parameters (OC-Softmax's centre): optimizer group 3 (src/main.py:418,456)
+        self.crit_params = ([p for p in self.criterion.parameters() if p.requires_grad]
+                            if isinstance(self.criterion, nn.Module) else [])
         self.group = world_group
         # --- parameter groups (main.py:416-457): wavlm_stream* at wavlm_lr, the rest at base_lr
         wl, bb = [], []
@@ -424,7 +542,7 @@ class Trainer:
                 (wl if "wavlm_stream" in n else bb).append(p)
         wavlm_lr = oc.get("wavlm_lr", 1e-6)
         groups = [{"params": wl, "lr": wavlm_lr}, {"params": bb, "lr": oc["base_lr"]},
-                  {"params": [], "lr": oc["base_lr"]}]
+                  {"params": list(self.crit_params), "lr": oc["base_lr"]}]
         if param_groups is not None:
             groups = param_groups
         if self.device.type == "cuda" and os.environ.get("RADHIP_ADAMW", "1") != "0":
@@ -465,22 +583,44 @@ class Trainer:
         self.scaler = torch.amp.GradScaler("cuda", enabled=(amp_dtype == torch.float16))
         self.ema = EMA(model, tc.get("ema_decay", 0.999)) if tc.get("use_ema", False) else None
         inert = {id(p) for p in no_grad_params(model)}     # never in the reference's graph: no .grad, no step
-        self.grads = FlatGrads([p for p in model.parameters() if id(p) not in inert])
-        self.params = self.grads.params
+        if isinstance(self.criterion, OCSoftmax):
+            # OC-Softmax reads the features alone: the classifier behind them gets no gradient in the reference
+            # (grad None: no AdamW step, no weight decay), so it gets no .grad here either. Every trainable tensor
+            # otherwise gets a view of the flat buffer (zeros count as a gradient: AdamW would decay it), so a model
+            # that cannot name those tensors is refused rather than trained differently from the reference
+            if not hasattr(model, "logit_only_parameters"):
+                raise ValueError(f"OC-Softmax needs {type(model).__name__}.logit_only_parameters(): the parameters "
+                                 "that only the logits depend on (they take no step), see models/DualStreamSEMamba.py")
+            inert |= {id(p) for p in model.logit_only_parameters()}
+        self.grads = FlatGrads([p for p in model.parameters() if id(p) not in inert], unclipped=self.crit_params)
+        self.params = self.grads.params                     # every tensor that takes a step, the centre included
+        crit = {id(p) for p in self.crit_params}
+        self.model_params = [p for p in self.params if id(p) not in crit]   # what clipping and SWA see
         self.micro = 0              # micro-batches since construction (resume state)
         self.epoch_micro = 0        # micro-batches of the current epoch: the reference's i + 1 (begin_epoch)
         self.loss_sum = torch.zeros((), device=self.device, dtype=torch.float64)
         self.n_seen = 0
 
-    def _loss(self, out, ya, yb, lam):
+    def _crit(self, out, feats, y):
+        return criterion_loss(self.criterion, self.supcon, self.lambda_supcon, out, feats, y)
+
+    def _loss(self, out, feats, ya, yb, lam):
         if ya is yb or lam == 1.0:
-            return self.criterion(out, ya)
-        return lam * self.criterion(out, ya) + (1 - lam) * self.criterion(out, yb)
+            return self._crit(out, feats, ya)
+        return lam * self._crit(out, feats, ya) + (1 - lam) * self._crit(out, feats, yb)
 
     def _fwd_loss(self, x, ya, yb, lam):
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype != torch.float32):
-            _, out = self.model(x, Freq_aug=self.freq_aug)
-            return self._loss(out, ya, yb, lam) / self.accum
+            feats, out = self.model(x, Freq_aug=self.freq_aug)
+            return self._loss(out, feats, ya, yb, lam) / self.accum
+
+    def feats_criteria(self):
+        """True when a criterion reads the features (OC-Softmax and / or SupCon)."""
+        return isinstance(self.criterion, OCSoftmax) or self.supcon is not None
+
+    def feat_loss(self, feats, ya, yb, lam, B):
+        """feats_loss for this trainer's criteria and accumulation steps."""
+        return feats_loss(self.criterion, self.supcon, self.lambda_supcon, self.accum, feats, ya, yb, lam, B)
 
     def mixup_draw(self, B):
         """lam ~ Beta(alpha, alpha) (numpy), perm = torch.randperm(B) (CPU generator) — main.py:1038-1046."""
@@ -557,7 +697,7 @@ class Trainer:
         if self.grads.bound():
             self.grads.clip_norm_(3.0)
         else:
-            torch.nn.utils.clip_grad_norm_(self.params, max_norm=3.0, foreach=True)
+            torch.nn.utils.clip_grad_norm_(self.model_params, max_norm=3.0, foreach=True)
         self.scaler.step(self.opt)
         self.scaler.update()
         self.grads.zero()
@@ -578,7 +718,9 @@ class Trainer:
         src/main.py:649-664): optimizer moments, LR schedule position, grad scaler, EMA."""
         return {"optimizer": self.opt.state_dict(), "scheduler": self.sched.state_dict(),
                 "scaler": self.scaler.state_dict(), "micro": self.micro,
-                "ema": self.ema.train_state() if self.ema is not None else None}
+                "ema": self.ema.train_state() if self.ema is not None else None,
+                "criterion": ({k: v.detach().clone() for k, v in self.criterion.state_dict().items()}
+                              if self.crit_params else None)}
 
     def load_state_dict(self, st):
         self.opt.load_state_dict(st["optimizer"])
@@ -589,6 +731,12 @@ class Trainer:
             raise ValueError("train state and config disagree on use_ema")
         if self.ema is not None:
             self.ema.load_train_state(st["ema"])
+        if self.crit_params:
+            if st.get("criterion") is None:
+                raise ValueError("train state carries no criterion state, the config's criterion has parameters")
+            with torch.no_grad():       # in place: captured graphs read the centre through its pointer
+                for k, v in self.criterion.state_dict().items():
+                    v.copy_(st["criterion"][k])
 
 
 @torch.no_grad()
@@ -777,8 +925,13 @@ class GraphedMicroStep:
         self._bind(k)
         tr.cnn_reuse(("use" if k == 1 else "store") if self.adv else None)
         with torch.autocast("cuda", dtype=tr.amp_dtype, enabled=tr.amp_dtype != torch.float32, cache_enabled=False):
-            _, out = tr.model(self.x, Freq_aug=tr.freq_aug)
-            loss = (self.lam * tr.criterion(out, self.ya) + (1.0 - self.lam) * tr.criterion(out, self.yb)) / tr.accum
+            feats, out = tr.model(self.x, Freq_aug=tr.freq_aug)
+            if isinstance(tr.criterion, OCSoftmax):
+                loss = tr.feat_loss(feats, self.ya, self.yb, self.lam, self.B)
+            else:
+                loss = (self.lam * tr.criterion(out, self.ya) + (1.0 - self.lam) * tr.criterion(out, self.yb)) / tr.accum
+                if tr.supcon is not None:
+                    loss = loss + tr.feat_loss(feats, self.ya, self.yb, self.lam, self.B)
         with ops.wgrad_batch():
             loss.backward()
         if k == 0:

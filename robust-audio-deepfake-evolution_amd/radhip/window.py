@@ -207,9 +207,24 @@ class WindowStep:
         from .train import FocalLoss
         return isinstance(self.tr.criterion, FocalLoss) and out.is_cuda and out.shape[1] <= 16
 
-    def _pass_loss(self, out, k=None):
+    def _pass_loss(self, out, feats, k=None):
         """The pass's loss / accum: micro-batch k's rows (adversarial pass) or all K (clean pass). The focal
-        criterion is one HIP launch per pass (ops.mixup_focal); any other criterion runs as modules."""
+        criterion is one HIP launch per pass (ops.mixup_focal), the criteria on the features (OC-Softmax as the
+        primary criterion, SupCon on top of any) one more (Trainer.feat_loss -> ops.mixup_ocsupcon); a cross-entropy
+        primary criterion runs as modules. Without a criterion on the features the launches are the focal ones
+        alone."""
+        tr = self.tr
+        if not tr.feats_criteria():
+            return self._logit_loss(out, k)
+        B = self.B
+        rows = slice(None) if k is None else slice(k * B, (k + 1) * B)
+        lam = self.lam if k is None else self.lam[k:k + 1]
+        from .train import OCSoftmax
+        primary = None if isinstance(tr.criterion, OCSoftmax) else self._logit_loss(out, k)
+        extra = tr.feat_loss(feats, self.ya[rows], self.yb[rows], lam, B)
+        return extra if primary is None else primary + extra
+
+    def _logit_loss(self, out, k=None):
         tr, B, K = self.tr, self.B, self.K
         if self._focal_fused(out):
             if k is None:
@@ -313,8 +328,8 @@ class WindowStep:
         core.encoder.keep_dev = self.c_keep
         try:
             with self._amp():
-                _, out = tr.model(self.x, Freq_aug=tr.freq_aug)
-                loss = self._pass_loss(out)
+                feats, out = tr.model(self.x, Freq_aug=tr.freq_aug)
+                loss = self._pass_loss(out, feats)
             with ops.wgrad_batch():
                 tr.scaler.scale(loss).backward()
             tr.loss_sum.add_(loss.detach().double() * (tr.accum * B))
@@ -347,8 +362,8 @@ class WindowStep:
             tr.model.sinc_given = self.f_adv_leaf[k]
         try:
             with self._amp():
-                _, out = tr.model(self.x[k * B:(k + 1) * B], Freq_aug=tr.freq_aug)
-                adv = self._pass_loss(out, k)
+                feats, out = tr.model(self.x[k * B:(k + 1) * B], Freq_aug=tr.freq_aug)
+                adv = self._pass_loss(out, feats, k)
             with ops.wgrad_batch():
                 tr.scaler.scale(adv).backward()
         finally:
