@@ -278,6 +278,27 @@ int rdx_ocsupcon_mixup_fwd(const void* feats, int feats_bf16, int ld, int R, int
 int rdx_ocsupcon_mixup_bwd(const float* grad, const float* dfeats, void* out, int out_bf16, int64_t n,
                            const float* dcenter_parts, int K, int D, float* dcenter, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention map and aggregation of a graph-attention layer (models/RawNetGatSpoofST.py:49-81 of the reference;
+ * AASIST's GraphAttentionLayer with its temperature), csrc/gat.hip. Per utterance, all fp32 and contiguous:
+ *   p[i,j,o] = b[o] + sum_d W[o,d] x[i,d] x[j,d]     s[i,j] = (sum_o w[o] tanh(p[i,j,o])) / temp
+ *   att[i,:] = softmax_j(s[i,:])                     agg[i,:] = sum_j att[i,j] x[j,:]
+ * x [B, N, Din], W [Dout, Din], b [Dout], w [Dout]; outputs att [B, N, N], agg [B, N, Din]. One workgroup per
+ * utterance; the [N, N, Dout] pair tensor is never written.
+ * rdx_gat_att_bwd: from dagg [B, N, Din] and the saved att (tanh recomputed), dx [B, N, Din] and the per-utterance
+ * partials dW [B, Dout, Din], db [B, Dout], dw [B, Dout] (the caller adds the B slots in a fixed order); dW, db and
+ * dw may all be NULL (dx only). No atomics: the same inputs give the same bits.
+ * rdx_gat_eligible states the supported shapes: 1 <= N <= 32, 1 <= Din <= 64, 1 <= Dout <= 64, temp > 0, x 16-byte
+ * aligned (as must be W and the dagg / att / agg / dx buffers); outside them the entries return RDX_EUNSUPPORTED.
+ * Both libraries export these entries; neither touches 16-bit storage.
+ * ------------------------------------------------------------------------------------------ */
+int rdx_gat_eligible(const void* x, int N, int Din, int Dout, float temp);
+int rdx_gat_att_fwd(const float* x, const float* W, const float* b, const float* w, float temp, int B, int N,
+                    int Din, int Dout, float* att, float* agg, void* stream);
+int rdx_gat_att_bwd(const float* dagg, const float* x, const float* W, const float* b, const float* w, float temp,
+                    const float* att, int B, int N, int Din, int Dout, float* dx, float* dW, float* db, float* dw,
+                    void* stream);
+
 /* ---- SincNet residual stack, NHWC fused epilogues (Residual_block.forward,
  * src/models/DualStreamSEMamba.py:182-200, with freeze_bn: src/main.py:44-51,1016-1018) -----------
  * Activations are [npix, C] row-major (channels_last), C % 8 == 0, C <= 512, 256 % (C/8) == 0.

@@ -210,6 +210,9 @@ SIGNATURES = {
     "rdx_ocsupcon_mixup_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int] + [c_f32] * 7
                                + [c_vp] * 5),
     "rdx_ocsupcon_mixup_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp, c_vp]),
+    "rdx_gat_eligible": (c_int, [c_vp, c_int, c_int, c_int, c_f32]),
+    "rdx_gat_att_fwd": (c_int, [c_vp] * 4 + [c_f32] + [c_int] * 4 + [c_vp] * 3),
+    "rdx_gat_att_bwd": (c_int, [c_vp] * 5 + [c_f32, c_vp] + [c_int] * 4 + [c_vp] * 5),
     "rdx_hgemm_x3": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int,
                              c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rdx_hgemm_batched": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_int,

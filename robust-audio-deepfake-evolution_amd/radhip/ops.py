@@ -640,6 +640,83 @@ def mixup_ocsupcon(feats, ya, yb, lam, rows_per_lam, oc, supcon, lambda_supcon, 
                                supcon.base_temperature if supcon is not None else 1.0, 1.0 / divisor)
 
 
+# ------------------------------------------------------------------------ graph attention ----
+def gat_eligible(x, att_proj, att_weight, temp=1.0):
+    """True when csrc/gat.hip takes this graph-attention layer: x a [B, N, Din] bf16 / fp16 / fp32 device tensor
+    (GatAtt casts it to contiguous fp32), att_proj a Linear(Din, Dout) with a bias, att_weight of Dout elements, and
+    the shape limits the library states (rdx_gat_eligible: N <= 32, Din <= 64, Dout <= 64, temp > 0). Callers take
+    the module path otherwise (CPU tensors, float64, larger graphs)."""
+    W, b = att_proj.weight, att_proj.bias
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype in (*HALF, torch.float32) and x.numel() > 0):
+        return False
+    if b is None or not (W.is_cuda and W.dim() == 2 and W.shape[1] == x.shape[2] and att_weight.is_cuda
+                         and att_weight.numel() == W.shape[0] and b.numel() == W.shape[0]):
+        return False
+    # the alignment rule is checked on a buffer of the allocator x's fp32 copy would come from
+    probe = x if x.dtype == torch.float32 and x.is_contiguous() else W
+    return bool(lib().rdx_gat_eligible(_p(probe), x.shape[1], x.shape[2], W.shape[0], float(temp)))
+
+
+class GatAtt(torch.autograd.Function):
+    """(agg, att) of one graph-attention layer on csrc/gat.hip, one workgroup per utterance:
+    att[b] = softmax_j((tanh(W (x_i * x_j) + bias) . w) / temp), agg[b] = att[b] @ x[b]. x [B, N, Din], W [Dout, Din],
+    bias [Dout], w [Dout], all contiguous fp32 on the device (gat_att prepares them); att is returned for inspection
+    and takes no gradient. The backward recomputes tanh from the saved att, writes each utterance's dW / dbias / dw
+    to its own slot and adds the slots with torch.sum over dim 0 (a fixed order): no atomics, the same bits every
+    time. Shapes outside gat_eligible raise (the C entry's RDX_EUNSUPPORTED)."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, w, temp):
+        _require_gpu(x, W, bias, w)
+        for t, what in ((x, "x"), (W, "W"), (bias, "bias"), (w, "w")):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"gat: {what} must be a contiguous fp32 tensor")
+        if x.dim() != 3 or W.dim() != 2 or W.shape[1] != x.shape[2] or bias.numel() != W.shape[0] or \
+                w.numel() != W.shape[0] or x.numel() == 0:
+            raise ValueError(f"gat: x [B, N, Din], W [Dout, Din], bias [Dout], w [Dout] required, got "
+                             f"{tuple(x.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}, {tuple(w.shape)}")
+        if not float(temp) > 0:
+            raise ValueError("gat: the temperature must be positive")
+        B, N, Din = x.shape
+        att = torch.empty(B, N, N, device=x.device, dtype=torch.float32)
+        agg = torch.empty(B, N, Din, device=x.device, dtype=torch.float32)
+        check(lib().rdx_gat_att_fwd(_p(x), _p(W), _p(bias), _p(w), float(temp), B, N, Din, W.shape[0], _p(att),
+                                    _p(agg), _stream(x)), "gat_att_fwd")
+        ctx.save_for_backward(x, W, bias, w, att)
+        ctx.temp = float(temp)
+        ctx.mark_non_differentiable(att)
+        return agg, att
+
+    @staticmethod
+    def backward(ctx, dagg, _datt):
+        x, W, bias, w, att = ctx.saved_tensors
+        B, N, Din = x.shape
+        Dout = W.shape[0]
+        dagg = dagg.float().contiguous()
+        dx = torch.empty_like(x)
+        parts = any(ctx.needs_input_grad[1:4])
+        dWp = torch.empty(B, Dout, Din, device=x.device, dtype=torch.float32) if parts else None
+        dbp = torch.empty(B, Dout, device=x.device, dtype=torch.float32) if parts else None
+        dwp = torch.empty(B, Dout, device=x.device, dtype=torch.float32) if parts else None
+        q = lambda t: _p(t) if t is not None else None
+        check(lib().rdx_gat_att_bwd(_p(dagg), _p(x), _p(W), _p(bias), _p(w), ctx.temp, _p(att), B, N, Din, Dout,
+                                    _p(dx), q(dWp), q(dbp), q(dwp), _stream(x)), "gat_att_bwd")
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dWp.sum(0) if need[1] else None,
+                dbp.sum(0).view_as(bias) if need[2] else None, dwp.sum(0).view_as(w) if need[3] else None, None)
+
+
+def gat_att(x, att_proj, att_weight, temp=1.0):
+    """GatAtt over a layer's own tensors: x may be a transposed view or a 16-bit autocast tensor (made contiguous
+    fp32 here, whatever autocast says), att_weight is the layer's [Dout, 1] parameter. Returns (agg, att) in fp32."""
+    if x.dim() != 3:
+        raise ValueError(f"gat: x must be [B, N, Din], got {tuple(x.shape)}")
+    if att_proj.bias is None:
+        raise ValueError("gat: att_proj needs a bias")
+    return GatAtt.apply(x.float().contiguous(), att_proj.weight.float().contiguous(),
+                        att_proj.bias.float().contiguous(), att_weight.float().reshape(-1), temp)
+
+
 # --------------------------------------------------------------------------- multi-tensor cast ----
 def cast_many(srcs, dsts):
     """dsts[k] = srcs[k] rounded to the dsts' 16-bit dtype (bf16 or fp16), fp32 contiguous sources, one launch per
