@@ -475,6 +475,14 @@ int rdx_wl_lora_grad(const void* dqkv, int64_t ldq, const void* x1, int64_t ldx,
                      float* dbq, float* dav, float* dbv, int64_t M, int E, int r, void* stream);
 int rdx_wl_lora_pack(int nl, const float* const* bq, const float* const* bv, void* const* wext, int64_t ldw,
                      int r, float scale, int E, void* stream);
+/* Launch geometry of the four row kernels (rdx_wl_ln1_fwd / _res_ln1_fwd, _add_ln_fwd, _ln_bwd, _ln1_bwd[_ex]):
+ * `waves` waves share a token row, `rows` rows share a workgroup. rdx_wl_rows_policy reports what a launch of
+ * `kernel` (0 LN1 forward, 1 add + LN forward, 2 LN backward, 3 LN1 backward) with M rows takes by default;
+ * rdx_wl_rows_override (measurement and tests, process-wide, not thread-safe) forces one geometry on all four
+ * until it is called with (0, 0); RDX_EINVAL for a geometry the library does not hold (a launch of a LoRA-active
+ * LN1 kernel under a forced geometry it does not hold answers RDX_EINVAL too). */
+int rdx_wl_rows_policy(int kernel, int64_t M, int lora, int* waves, int* rows);
+int rdx_wl_rows_override(int waves, int rows);
 
 /* ---- bf16 MFMA GEMM with fused epilogues: the WavLM layer's projections (q|k|v + LoRA columns,
  * out_proj, FFN1, FFN2 of HF WavLMEncoderLayerStableLayerNorm, src/models/DualStreamSEMamba.py:292-439)

@@ -8,9 +8,12 @@
 //     [q k v] = x1 [Wq Wk Wv]^T + b + s * (B_q A_q drop(x1), 0, B_v A_v drop(x1))
 //     h2 = h + drop(out_proj(attn(q, k, v, gate)));  x2 = LN2(h2)
 //     h' = h2 + drop(W2 gelu(W1 x2 + b1) + b2)
-// Layout: one wave per token row (E = 1024 = 64 lanes x 16 contiguous fp32), so a row's LN
-// statistics, its 16 per-head gates (4 lanes per 64-dim head) and its 2r = 16 LoRA down-projections
-// are wave reductions. The LoRA down-projection a = A drop(x1) is written next to x1 into one
+// Layout: one, two or four waves per token row (E = 1024 = 4 chunks of 64 lanes x 4 contiguous fp32, see
+// "Row layout" below), so a row's LN statistics and its 2r = 16 LoRA down-projections are wave
+// reductions (combined through LDS when waves share a row) and its 16 per-head gates sums over
+// 16-lane rows. The
+// (combined through LDS when waves share a row) and its 16 per-head gates sums over 16-lane rows.
+// The LoRA down-projection a = A drop(x1) is written next to x1 into one
 // [M, E + 2r] bf16 operand, so the q/k/v GEMM (K = E + 2r against [Wqkv | s B]) applies the whole
 // LoRA update with no extra GEMM; its backward returns d a in the same GEMM.
 // Dropout: counter-hash masks (common.h) keyed by (layer seed, salt, m * E + e), regenerated in the
@@ -34,75 +37,90 @@ __device__ __forceinline__ float drop_scale(const Drop& d, uint64_t seed, uint64
   return drop_keep(seed, idx, d.thr) ? d.inv_keep : 0.f;
 }
 
-__device__ __forceinline__ void load16(const float* p, float* v) {
-  const float4* q = reinterpret_cast<const float4*>(p);
+// ---- Row layout of the row kernels --------------------------------------------------------------------------------
+// A row is 4 chunks of WL_CHUNK = 256 elements; in chunk c lane l owns the 4 elements c * 256 + 4 l .. + 3, so one
+// 16-byte fp32 instruction of a wave covers one contiguous 1 KB span and one 8-byte 16-bit instruction a contiguous
+// 512 B span (lane-owns-16-contiguous touched 32 cache lines per instruction, the same 32 four times per row).
+// W = 1, 2 or 4 waves share a row: wave w of the row owns the N = 4 / W chunks w * N .. w * N + N - 1, and a lane's
+// value k (0 .. 4 N - 1) is element e0 + wl_elem(k), e0 = w * N * 256 + 4 lane. The helpers below take the lane's
+// pointer (row + e0).
+constexpr int WL_CHUNK = 4 * RDX_WAVE;
+__device__ __forceinline__ constexpr int wl_elem(int k) { return (k >> 2) * WL_CHUNK + (k & 3); }
+
+template <int N>
+__device__ __forceinline__ void load_chunks(const float* p, float* v) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float4 t = q[i];
-    v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+  for (int j = 0; j < N; ++j) {
+    const float4 t = *reinterpret_cast<const float4*>(p + j * WL_CHUNK);
+    v[4 * j] = t.x; v[4 * j + 1] = t.y; v[4 * j + 2] = t.z; v[4 * j + 3] = t.w;
   }
 }
-__device__ __forceinline__ void store16(float* p, const float* v) {
-  float4* q = reinterpret_cast<float4*>(p);
+template <int N>
+__device__ __forceinline__ void store_chunks(float* p, const float* v) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+  for (int j = 0; j < N; ++j)
+    *reinterpret_cast<float4*>(p + j * WL_CHUNK) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
 }
-__device__ __forceinline__ void load16_bf(const hst* p, float* v) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint4 t = q[i];
-    uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[8 * i + 2 * j] = hlo(w[j]);
-      v[8 * i + 2 * j + 1] = hhi(w[j]);
-    }
-  }
-}
-// raw 16 bf16 (two 16-byte loads), unpacked later: keeps the unpack from pinning a wait between a row's loads
-struct Bf16x16 {
-  uint4 q[2];
+// raw 16-bit chunks (one 8-byte load each), unpacked later: keeps the unpack from pinning a wait between a row's loads
+template <int N>
+struct HChunks {
+  uint2 q[N];
 };
-__device__ __forceinline__ Bf16x16 load16_bf_raw(const hst* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  return Bf16x16{{q[0], q[1]}};
+template <int N>
+__device__ __forceinline__ HChunks<N> load_chunks_h_raw(const hst* p) {
+  HChunks<N> t;
+#pragma unroll
+  for (int j = 0; j < N; ++j) t.q[j] = *reinterpret_cast<const uint2*>(p + j * WL_CHUNK);
+  return t;
 }
-__device__ __forceinline__ void unpack16_bf(const Bf16x16& t, float* v) {
+template <int N>
+__device__ __forceinline__ void unpack_chunks_h(const HChunks<N>& t, float* v) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint32_t w[4] = {t.q[i].x, t.q[i].y, t.q[i].z, t.q[i].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[8 * i + 2 * j] = hlo(w[j]);
-      v[8 * i + 2 * j + 1] = hhi(w[j]);
-    }
+  for (int j = 0; j < N; ++j) {
+    v[4 * j] = hlo(t.q[j].x);
+    v[4 * j + 1] = hhi(t.q[j].x);
+    v[4 * j + 2] = hlo(t.q[j].y);
+    v[4 * j + 3] = hhi(t.q[j].y);
   }
 }
-__device__ __forceinline__ void store16_bf(hst* p, const float* v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
+template <int N>
+__device__ __forceinline__ void store_chunks_h(hst* p, const float* v) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = hbits(v[8 * i + 2 * j]) | (hbits(v[8 * i + 2 * j + 1]) << 16);
-    q[i] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  for (int j = 0; j < N; ++j)
+    *reinterpret_cast<uint2*>(p + j * WL_CHUNK) =
+        make_uint2(hbits(v[4 * j]) | (hbits(v[4 * j + 1]) << 16), hbits(v[4 * j + 2]) | (hbits(v[4 * j + 3]) << 16));
 }
 
-// mean / rstd of a row held as 16 values per lane (two-pass, biased variance like torch)
-__device__ __forceinline__ void row_stats(const float* v, float eps, float& mean, float& rstd) {
+// Total of the W row-waves' wave sums (every lane of a wave holds `part`), through this row's W LDS slots with one
+// barrier, added in wave order 0 .. W - 1 by everyone: all lanes of the row get the bit-identical total and two runs
+// agree. Every wave of the workgroup calls it (a dead row's waves too: the barrier). W = 1 is the plain wave sum.
+template <int W>
+__device__ __forceinline__ float row_total(float part, float* slots, int w, int lane) {
+  if (W == 1) return part;
+  if (lane == 0) slots[w] = part;
+  __syncthreads();
+  float t = slots[0];
+#pragma unroll
+  for (int k = 1; k < W; ++k) t += slots[k];
+  return t;
+}
+
+// mean / rstd of a row held as 16 / W values per lane of W waves (two-pass, biased variance like torch); slots: this
+// row's [2][W] floats of LDS
+template <int W>
+__device__ __forceinline__ void row_stats(const float* v, float eps, float& mean, float& rstd, float* slots, int w,
+                                          int lane) {
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) s += v[i];
-  mean = wave_sum(s) * (1.0f / WL_E);
+  for (int i = 0; i < WL_VPL / W; ++i) s += v[i];
+  mean = row_total<W>(wave_sum(s), slots, w, lane) * (1.0f / WL_E);
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) {
+  for (int i = 0; i < WL_VPL / W; ++i) {
     float d = v[i] - mean;
     q += d * d;
   }
-  rstd = rsqrtf(wave_sum(q) * (1.0f / WL_E) + eps);
+  rstd = rsqrtf(row_total<W>(wave_sum(q), slots + W, w, lane) * (1.0f / WL_E) + eps);
 }
 
 // Sum 16 per-lane values over the wave with 17 shuffles: lane l ends with the total of index
@@ -141,21 +159,25 @@ struct GateW {
   const float* gconst;  // [H] gru_rel_pos_const
 };
 
-// gate pre-activations z[8] of this lane's head (4 lanes per head, 16 dims per lane); wg in LDS or global
-__device__ __forceinline__ void gate_z(const GateW& g, const float* wgp, const float* x, int lane, float* z) {
-  const int part = lane & 3;
+// The two gate pre-activation sums (za = z0 + .. + z3, zb = z4 + .. + z7) of the head of each of the lane's N chunks:
+// a chunk holds 4 heads, one per 16-lane DPP row (head = 4 chunk + lane / 16, the lane's 4 dims at 4 (lane % 16)), so
+// a head's dot products are row sums; wg in LDS. Every lane of the row gets both sums. Call with the whole wave active.
+template <int N>
+__device__ __forceinline__ void gate_z(const GateW& g, const float* wgp, const float* x, int lane, float* za,
+                                       float* zb) {
+  const int d0 = (lane & 15) * 4;
+  float4 w[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float4* w = reinterpret_cast<const float4*>(wgp + j * 64 + part * 16);
-    float acc = 0.f;
+  for (int j = 0; j < 8; ++j) w[j] = *reinterpret_cast<const float4*>(wgp + j * 64 + d0);
+  const float ba = g.bg[0] + g.bg[1] + g.bg[2] + g.bg[3], bb = g.bg[4] + g.bg[5] + g.bg[6] + g.bg[7];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float4 t = w[i];
-      acc += t.x * x[4 * i] + t.y * x[4 * i + 1] + t.z * x[4 * i + 2] + t.w * x[4 * i + 3];
-    }
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    z[j] = acc + g.bg[j];
+  for (int c = 0; c < N; ++c) {
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      s[j >> 2] += w[j].x * x[4 * c] + w[j].y * x[4 * c + 1] + w[j].z * x[4 * c + 2] + w[j].w * x[4 * c + 3];
+    za[c] = row16_sum(s[0]) + ba;
+    zb[c] = row16_sum(s[1]) + bb;
   }
 }
 
@@ -187,14 +209,10 @@ struct Ln1Args {
 // the fp32 A from L2 itself moved 64 KB per token row and left these kernels L2-bound (26 us of the 47 us forward
 // at B = 32); staging it from fp32 with the conversion here still read 64 KB per workgroup.
 #ifndef WL_LN1_ROWS_DEF
-#define WL_LN1_ROWS_DEF 4   // measured: 4 rows beat 8 and 2 at both pass sizes (tools/bench_wl.py)
-#endif
+#define WL_LN1_ROWS_DEF 4   // rows per workgroup of the LoRA-active LN1 kernels (one wave per row): measured, 4 rows
+#endif                      // beat 8 and 2 at both pass sizes (tools/bench_wl.py)
 constexpr int WL_LN1_ROWS = WL_LN1_ROWS_DEF;
-constexpr int WL_LN1_THREADS = WL_LN1_ROWS * RDX_WAVE;
 
-// WL_R2 * WL_E 16-bit values over WL_LN1_THREADS threads, 8 per 16-byte load, every load issued before the first
-// store: a loop that stored each chunk as it arrived waited out one L2 round trip per chunk (8 per thread), which
-// was most of the LoRA kernels' extra time over the LoRA-free variant
 // The staging of a LN1 workgroup, gate weights (2 KB fp32) and LoRA-A (32 KB 16-bit), straight from global memory
 // into LDS by buffer_load ... lds (16 bytes per lane, lane-linear: one wave-instruction fills 1 KB), issued before the
 // rows' own loads and retired by the waitcnt ahead of the barrier: every load of the prologue in flight at once and
@@ -213,12 +231,12 @@ __device__ __forceinline__ wl_i32x4 wl_rsrc(const void* base, uint32_t bytes) {
   r.w = 0x00020000;  // raw buffer, range-checked
   return r;
 }
-constexpr int WL_A_INSTR = WL_R2 * WL_E * 2 / 1024 / (WL_LN1_THREADS / 64);   // LoRA-A instructions per wave (8)
-static_assert(WL_A_INSTR * 1024 * (WL_LN1_THREADS / 64) == WL_R2 * WL_E * 2, "whole 1 KB instructions per wave");
-template <bool kLora>
+template <bool kLora, int NW>   // NW: waves of the workgroup
 __device__ __forceinline__ void stage_dma(float* swg, hst* sA, const float* wg, const hst* Aq, const hst* Av) {
+  constexpr int WL_A_INSTR = WL_R2 * WL_E * 2 / 1024 / NW;   // LoRA-A instructions per wave (8 at 4 waves)
+  static_assert(!kLora || (NW == WL_LN1_ROWS && WL_A_INSTR % 2 == 0 && WL_A_INSTR * 1024 * NW == WL_R2 * WL_E * 2),
+                "LoRA-A is staged by WL_LN1_ROWS one-wave rows: whole 1 KB instructions, half per adapter");
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  constexpr int NW = WL_LN1_THREADS / 64;
   if (wv == 0) {
     const wl_i32x4 rg = wl_rsrc(wg, 8 * 64 * 4);
 #pragma unroll
@@ -239,65 +257,74 @@ __device__ __forceinline__ void stage_dma(float* swg, hst* sA, const float* wg, 
   }
 }
 
-template <bool kLora>
-__global__ __launch_bounds__(WL_LN1_THREADS) void wl_ln1_fwd_kernel(Ln1Args a) {
+// W waves per row, R rows per workgroup (see the row layout above). Dead rows (m >= M) run to the end with zeros and
+// store nothing: the row reductions and the LoRA combine have barriers.
+template <bool kLora, int W, int R>
+__global__ __launch_bounds__(W * R * RDX_WAVE) void wl_ln1_fwd_kernel(Ln1Args a) {
+  constexpr int N = 4 / W, NV = WL_VPL / W;   // chunks and values per lane
   __shared__ __attribute__((aligned(16))) hst sA[kLora ? WL_R2 * WL_E : 8];
   __shared__ __attribute__((aligned(16))) float swg[8 * 64];
-  const int lane = threadIdx.x & 63;
-  const int64_t m = (int64_t)blockIdx.x * WL_LN1_ROWS + (threadIdx.x >> 6);
+  __shared__ float sred[R][2 * W];
+  static_assert(!kLora || W == 1, "the LoRA-active kernels run one wave per row (no geometry measured faster)");
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, row = wv / W, w = wv % W;
+  const int64_t m = (int64_t)blockIdx.x * R + row;
   const bool live = m < a.M;  // no early return: the gate and LoRA parts follow a barrier
-  const int e0 = lane * WL_VPL;
-  float v[WL_VPL], gm[WL_VPL], bt[WL_VPL], dl[WL_VPL];
-  Bf16x16 dlr;
+  const int e0 = w * N * WL_CHUNK + lane * 4;
+  float v[NV], gm[NV], bt[NV], dl[NV];
+  HChunks<N> dlr;
   const uint64_t sr = (a.h2 && a.dres.thr) ? attn_seed(a.dres.seed_dev, a.dres.salt) : 0;  // with the row loads
   // every global load first (one round trip): the workgroup's staging, the row, the affine parameters
-  stage_dma<kLora>(swg, sA, a.g.wg, a.Aq, a.Av);
+  stage_dma<kLora, W * R>(swg, sA, a.g.wg, a.Aq, a.Av);
   if (live) {
-    load16(a.h2 ? a.h2 + m * WL_E + e0 : a.h + m * WL_E + e0, v);
-    if (a.h2) dlr = load16_bf_raw(a.delta + m * WL_E + e0);
-    load16(a.gamma + e0, gm);
-    load16(a.beta + e0, bt);
+    load_chunks<N>(a.h2 ? a.h2 + m * WL_E + e0 : a.h + m * WL_E + e0, v);
+    if (a.h2) dlr = load_chunks_h_raw<N>(a.delta + m * WL_E + e0);
+    load_chunks<N>(a.gamma + e0, gm);
+    load_chunks<N>(a.beta + e0, bt);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = 0.f;
   }
   __builtin_amdgcn_s_waitcnt(0);   // the staging DMA (and the row) landed
   __syncthreads();
+  if (live && a.h2) {
+    unpack_chunks_h<N>(dlr, dl);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      v[i] += dl[i] * (a.dres.thr ? drop_scale(a.dres, sr, (uint64_t)m * WL_E + e0 + wl_elem(i)) : 1.0f);
+    store_chunks<N>(a.hout + m * WL_E + e0, v);
+  }
+  float mean, rstd;
+  row_stats<W>(v, a.eps, mean, rstd, sred[row], w, lane);
   if (live) {
-    if (a.h2) {
-      unpack16_bf(dlr, dl);
-
 #pragma unroll
-      for (int i = 0; i < WL_VPL; ++i)
-        v[i] += dl[i] * (a.dres.thr ? drop_scale(a.dres, sr, (uint64_t)m * WL_E + e0 + i) : 1.0f);
-      store16(a.hout + m * WL_E + e0, v);
-    }
-    float mean, rstd;
-    row_stats(v, a.eps, mean, rstd);
-#pragma unroll
-    for (int i = 0; i < WL_VPL; ++i) v[i] = hround((v[i] - mean) * rstd * gm[i] + bt[i]);
-    store16_bf(a.x1 + m * a.ldx + e0, v);
-    if (lane == 0) {
+    for (int i = 0; i < NV; ++i) v[i] = hround((v[i] - mean) * rstd * gm[i] + bt[i]);
+    store_chunks_h<N>(a.x1 + m * a.ldx + e0, v);
+    if (w == 0 && lane == 0) {
       a.mean[m] = mean;
       a.rstd[m] = rstd;
     }
-    float z[8];
-    gate_z(a.g, swg, v, lane, z);
-    if ((lane & 3) == 0) {
-      const int head = lane >> 2;
-      float ga = sigmoidf_(z[0] + z[1] + z[2] + z[3]);
-      float gb = sigmoidf_(z[4] + z[5] + z[6] + z[7]);
-      a.gate[m * (WL_E / 64) + head] = ga * (gb * a.g.gconst[head] - 1.0f) + 2.0f;
+    float za[N], zb[N];
+    gate_z<N>(a.g, swg, v, lane, za, zb);
+    if ((lane & 15) == 0) {
+#pragma unroll
+      for (int c = 0; c < N; ++c) {
+        const int head = (w * N + c) * 4 + (lane >> 4);
+        const float ga = sigmoidf_(za[c]), gb = sigmoidf_(zb[c]);
+        a.gate[m * (WL_E / 64) + head] = ga * (gb * a.g.gconst[head] - 1.0f) + 2.0f;
+      }
     }
   }
   if (kLora) {
     if (!live) return;
     const uint64_t sq = a.dq.thr ? attn_seed(a.dq.seed_dev, a.dq.salt) : 0;
     const uint64_t sv = a.dv.thr ? attn_seed(a.dv.seed_dev, a.dv.salt) : 0;
-    // each adapter's dropped row in the 16-bit type (the reference's dropout output: lora_A's input under autocast),
-    // packed in pairs, and the down-projection as packed dot products (v_dot2c_f32_*: 8 per adapter row instead of
-    // 16 unpacks + 16 FMAs; the per-row VALU work of these 2r dot products was the LoRA kernels' extra time)
-    uint32_t mq[WL_VPL / 2], mv[WL_VPL / 2];
+    // each adapter's dropped row in the 16-bit type (the reference's dropout output: lora_A's input under
+    // autocast), packed in pairs, and the down-projection as packed dot products (v_dot2c_f32_*: one per pair
+    // instead of 2 unpacks + 2 FMAs; the per-row VALU work of these 2r dot products was the LoRA kernels' extra time)
+    uint32_t mq[NV / 2], mv[NV / 2];
 #pragma unroll
-    for (int j = 0; j < WL_VPL / 2; ++j) {
-      const uint64_t idx = (uint64_t)m * WL_E + e0 + 2 * j;
+    for (int j = 0; j < NV / 2; ++j) {
+      const uint64_t idx = (uint64_t)m * WL_E + e0 + wl_elem(2 * j);
       mq[j] = hpack2(v[2 * j] * drop_scale(a.dq, sq, idx), v[2 * j + 1] * drop_scale(a.dq, sq, idx + 1));
       mv[j] = hpack2(v[2 * j] * drop_scale(a.dv, sv, idx), v[2 * j + 1] * drop_scale(a.dv, sv, idx + 1));
     }
@@ -305,15 +332,16 @@ __global__ __launch_bounds__(WL_LN1_THREADS) void wl_ln1_fwd_kernel(Ln1Args a) {
 #pragma unroll
     for (int k = 0; k < WL_R2; ++k) {
       const uint32_t* x = k < WL_R2 / 2 ? mq : mv;
-      const uint4* wp = reinterpret_cast<const uint4*>(sA + k * WL_E + e0);
-      const uint4 w0 = wp[0], w1 = wp[1];
-      const uint32_t w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
       float s = 0.f;
 #pragma unroll
-      for (int j = 0; j < WL_VPL / 2; ++j) s = hdot2(w[j], x[j], s);
+      for (int c = 0; c < N; ++c) {   // 8 bytes per lane, lane-linear: conflict-free
+        const uint2 wk = *reinterpret_cast<const uint2*>(sA + k * WL_E + e0 + c * WL_CHUNK);
+        s = hdot2(wk.x, x[2 * c], s);
+        s = hdot2(wk.y, x[2 * c + 1], s);
+      }
       acc[k] = s;
     }
-    float tot = wave_sum16(acc, lane);
+    const float tot = wave_sum16(acc, lane);
     if ((lane & 3) == 0) a.x1[m * a.ldx + WL_E + sum16_index(lane)] = f2h(tot);
   }
 }
@@ -333,32 +361,43 @@ struct AddLnArgs {
   int64_t M;
 };
 
-__global__ __launch_bounds__(256) void wl_add_ln_fwd_kernel(AddLnArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= a.M) return;
-  const int e0 = lane * WL_VPL;
-  float v[WL_VPL], dl[WL_VPL], gm[WL_VPL], bt[WL_VPL];
-  load16(a.h + m * WL_E + e0, v);
-  const Bf16x16 dlr = load16_bf_raw(a.delta + m * WL_E + e0);
-  load16(a.gamma + e0, gm);   // with the row's loads: one round trip
-  load16(a.beta + e0, bt);
-  unpack16_bf(dlr, dl);
-  const uint64_t seed = a.d.thr ? attn_seed(a.d.seed_dev, a.d.salt) : 0;
+template <int W, int R>
+__global__ __launch_bounds__(W * R * RDX_WAVE) void wl_add_ln_fwd_kernel(AddLnArgs a) {
+  constexpr int N = 4 / W, NV = WL_VPL / W;
+  __shared__ float sred[R][2 * W];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, row = wv / W, w = wv % W;
+  const int64_t m = (int64_t)blockIdx.x * R + row;
+  const bool live = m < a.M;
+  if (W == 1 && !live) return;   // more waves per row: dead rows reach the reductions' barriers
+  const int e0 = w * N * WL_CHUNK + lane * 4;
+  float v[NV], dl[NV], gm[NV], bt[NV];
+  if (live) {
+    load_chunks<N>(a.h + m * WL_E + e0, v);
+    const HChunks<N> dlr = load_chunks_h_raw<N>(a.delta + m * WL_E + e0);
+    load_chunks<N>(a.gamma + e0, gm);   // with the row's loads: one round trip
+    load_chunks<N>(a.beta + e0, bt);
+    unpack_chunks_h<N>(dlr, dl);
+    const uint64_t seed = a.d.thr ? attn_seed(a.d.seed_dev, a.d.salt) : 0;
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i)
-    v[i] += dl[i] * (a.d.thr ? drop_scale(a.d, seed, (uint64_t)m * WL_E + e0 + i) : 1.0f);
-  store16(a.h2 + m * WL_E + e0, v);
+    for (int i = 0; i < NV; ++i)
+      v[i] += dl[i] * (a.d.thr ? drop_scale(a.d, seed, (uint64_t)m * WL_E + e0 + wl_elem(i)) : 1.0f);
+    store_chunks<N>(a.h2 + m * WL_E + e0, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = 0.f;
+  }
   float mean, rstd;
-  row_stats(v, a.eps, mean, rstd);
+  row_stats<W>(v, a.eps, mean, rstd, sred[row], w, lane);
+  if (!live) return;
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) v[i] = (v[i] - mean) * rstd * gm[i] + bt[i];
-  store16_bf(a.x + m * WL_E + e0, v);
-  if (lane == 0) {
+  for (int i = 0; i < NV; ++i) v[i] = (v[i] - mean) * rstd * gm[i] + bt[i];
+  store_chunks_h<N>(a.x + m * WL_E + e0, v);
+  if (w == 0 && lane == 0) {
     a.mean[m] = mean;
     a.rstd[m] = rstd;
   }
 }
+
 
 // out = h + drop(delta) over n = M * E elements (8 per thread)
 __global__ __launch_bounds__(256) void wl_residual_kernel(const float* __restrict__ h,
@@ -449,47 +488,80 @@ struct LnBwdArgs {
   int64_t M;
 };
 
+// slots: this row's [2][W] floats of LDS (both sums cross the waves behind one barrier)
+template <int W>
 __device__ __forceinline__ void ln_bwd_row(const float* dx, const float* x, float mean, float rstd, const float* gm,
-                                           float* out) {
-  float g[WL_VPL], xh[WL_VPL], s1 = 0.f, s2 = 0.f;
+                                           float* out, float* slots, int w, int lane) {
+  constexpr int NV = WL_VPL / W;
+  float g[NV], xh[NV], s1 = 0.f, s2 = 0.f;
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) {
+  for (int i = 0; i < NV; ++i) {
     xh[i] = (x[i] - mean) * rstd;
     g[i] = dx[i] * gm[i];
     s1 += g[i];
     s2 += g[i] * xh[i];
   }
-  s1 = wave_sum(s1) * (1.0f / WL_E);
-  s2 = wave_sum(s2) * (1.0f / WL_E);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  if (W > 1) {
+    if (lane == 0) {
+      slots[w] = s1;
+      slots[W + w] = s2;
+    }
+    __syncthreads();
+    s1 = slots[0];
+    s2 = slots[W];
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) out[i] = rstd * (g[i] - s1 - xh[i] * s2);
+    for (int k = 1; k < W; ++k) {   // wave order, by everyone: bit-identical in every lane and every run
+      s1 += slots[k];
+      s2 += slots[W + k];
+    }
+  }
+  s1 *= 1.0f / WL_E;
+  s2 *= 1.0f / WL_E;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) out[i] = rstd * (g[i] - s1 - xh[i] * s2);
 }
 
-__global__ __launch_bounds__(256) void wl_ln_bwd_kernel(LnBwdArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= a.M) return;
-  const int e0 = lane * WL_VPL;
-  float dx[WL_VPL], x[WL_VPL], gm[WL_VPL], o[WL_VPL], r[WL_VPL];
+template <int W, int R>
+__global__ __launch_bounds__(W * R * RDX_WAVE) void wl_ln_bwd_kernel(LnBwdArgs a) {
+  constexpr int N = 4 / W, NV = WL_VPL / W;
+  __shared__ float sred[R][2 * W];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, row = wv / W, w = wv % W;
+  const int64_t m = (int64_t)blockIdx.x * R + row;
+  const bool live = m < a.M;
+  if (W == 1 && !live) return;   // more waves per row: dead rows reach the reduction's barrier
+  const int e0 = w * N * WL_CHUNK + lane * 4;
+  float dx[NV], x[NV], gm[NV], o[NV], r[NV];
+  float mean = 0.f, rstd = 0.f;
   const uint64_t seed = (a.ddrop && a.d.thr) ? attn_seed(a.d.seed_dev, a.d.salt) : 0;
-  const Bf16x16 dxr = load16_bf_raw(a.dx + m * a.ldd + e0);
-  load16(a.h + m * WL_E + e0, x);
-  load16(a.gamma + e0, gm);
-  if (a.dres) load16(a.dres + m * WL_E + e0, r);     // every load of the row before the reductions
-  unpack16_bf(dxr, dx);
-  ln_bwd_row(dx, x, a.mean[m], a.rstd[m], gm, o);
+  if (live) {
+    const HChunks<N> dxr = load_chunks_h_raw<N>(a.dx + m * a.ldd + e0);
+    load_chunks<N>(a.h + m * WL_E + e0, x);
+    load_chunks<N>(a.gamma + e0, gm);
+    if (a.dres) load_chunks<N>(a.dres + m * WL_E + e0, r);     // every load of the row before the reductions
+    mean = a.mean[m];
+    rstd = a.rstd[m];
+    unpack_chunks_h<N>(dxr, dx);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) dx[i] = x[i] = gm[i] = 0.f;
+  }
+  ln_bwd_row<W>(dx, x, mean, rstd, gm, o, sred[row], w, lane);
+  if (!live) return;
   if (a.dres) {
 #pragma unroll
-    for (int i = 0; i < WL_VPL; ++i) o[i] += r[i];
+    for (int i = 0; i < NV; ++i) o[i] += r[i];
   }
-  store16(a.dh + m * WL_E + e0, o);
+  store_chunks<N>(a.dh + m * WL_E + e0, o);
   if (a.ddrop) {
 #pragma unroll
-    for (int i = 0; i < WL_VPL; ++i)
-      o[i] *= a.d.thr ? drop_scale(a.d, seed, (uint64_t)m * WL_E + e0 + i) : 1.0f;
-    store16_bf(a.ddrop + m * WL_E + e0, o);
+    for (int i = 0; i < NV; ++i)
+      o[i] *= a.d.thr ? drop_scale(a.d, seed, (uint64_t)m * WL_E + e0 + wl_elem(i)) : 1.0f;
+    store_chunks_h<N>(a.ddrop + m * WL_E + e0, o);
   }
 }
+
 
 // LN1 backward: dx1 = dX1[:, :E] + gate backward + LoRA-A backward; dh = dres + LN1_bwd(dx1).
 // Also writes the dropped LN output of each adapter (xd[0] q, xd[1] v) for the dA GEMMs.
@@ -519,123 +591,135 @@ struct Ln1BwdArgs {
   hst* ddrop;
 };
 
-template <bool kLora>
-__global__ __launch_bounds__(WL_LN1_THREADS) void wl_ln1_bwd_kernel(Ln1BwdArgs a) {
+template <bool kLora, int W, int R>
+__global__ __launch_bounds__(W * R * RDX_WAVE) void wl_ln1_bwd_kernel(Ln1BwdArgs a) {
+  static_assert(!kLora || W == 1, "the LoRA-active kernels run one wave per row");
+  constexpr int N = 4 / W, NV = WL_VPL / W;
   __shared__ __attribute__((aligned(16))) hst sA[kLora ? WL_R2 * WL_E : 8];
   __shared__ __attribute__((aligned(16))) float swg[8 * 64];
-  const int lane = threadIdx.x & 63;
-  const int64_t m = (int64_t)blockIdx.x * WL_LN1_ROWS + (threadIdx.x >> 6);
+  __shared__ float sred[R][2 * W];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, row = wv / W, w = wv % W;
+  const int64_t m = (int64_t)blockIdx.x * R + row;
   const bool live = m < a.M;
-  const int e0 = lane * WL_VPL;
-  const int part = lane & 3, head = lane >> 2;
+  const int e0 = w * N * WL_CHUNK + lane * 4;
+  const int d0 = (lane & 15) * 4, head0 = w * N * 4 + (lane >> 4);   // chunk c of the lane: head head0 + 4 c
   // every row load first: h, dx1, the residual gradient, the layer-sum gradient, the affine parameters
-  float x[WL_VPL], x1[WL_VPL], dx[WL_VPL], r[WL_VPL], sgv[WL_VPL], gm[WL_VPL];
-  float mean = 0.f, rstd = 0.f, dg = 0.f;
-  Bf16x16 dxr;
+  float x[NV], x1[NV], dx[NV], r[NV], sgv[NV], gm[NV], dg[N];
+  float mean = 0.f, rstd = 0.f;
+  HChunks<N> dxr;
   const uint64_t sp = (a.ddrop && a.dprev.thr) ? attn_seed(a.dprev.seed_dev, a.dprev.salt) : 0;
-  stage_dma<kLora>(swg, sA, a.g.wg, a.Aq, a.Av);
+  stage_dma<kLora, W * R>(swg, sA, a.g.wg, a.Aq, a.Av);
   if (live) {
-    load16(a.h + m * WL_E + e0, x);
-    dxr = load16_bf_raw(a.dx1 + m * a.ldx + e0);
-    load16(a.dres + m * WL_E + e0, r);
-    if (a.sg) load16(a.sg + m * WL_E + e0, sgv);
-    load16(a.gamma + e0, gm);
-    load16(a.beta + e0, x1);
+    load_chunks<N>(a.h + m * WL_E + e0, x);
+    dxr = load_chunks_h_raw<N>(a.dx1 + m * a.ldx + e0);
+    load_chunks<N>(a.dres + m * WL_E + e0, r);
+    if (a.sg) load_chunks<N>(a.sg + m * WL_E + e0, sgv);
+    load_chunks<N>(a.gamma + e0, gm);
+    load_chunks<N>(a.beta + e0, x1);
     mean = a.mean[m];
     rstd = a.rstd[m];
-    dg = a.dgate[m * (WL_E / 64) + head];
+#pragma unroll
+    for (int c = 0; c < N; ++c) dg[c] = a.dgate[m * (WL_E / 64) + head0 + 4 * c];
   }
   __builtin_amdgcn_s_waitcnt(0);   // the staging DMA (and the row) landed
   __syncthreads();
-  if (!live) return;  // after the only barrier
-  unpack16_bf(dxr, dx);
+  if (W == 1 && !live) return;  // more waves per row: dead rows go on to the reduction's barrier with zeros
+  if (live) {
+    unpack_chunks_h<N>(dxr, dx);
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) x1[i] = hround((x[i] - mean) * rstd * gm[i] + x1[i]);
-  // gate: gate = ga (gb c - 1) + 2
-  float z[8];
-  gate_z(a.g, swg, x1, lane, z);
-  const float ga = sigmoidf_(z[0] + z[1] + z[2] + z[3]), gb = sigmoidf_(z[4] + z[5] + z[6] + z[7]);
-  const float c = a.g.gconst[head];
-  const float dza = dg * (gb * c - 1.0f) * ga * (1.0f - ga);
-  const float dzb = dg * ga * c * gb * (1.0f - gb);
-#pragma unroll 2
-  for (int j = 0; j < 8; ++j) {
-    const float dz = j < 4 ? dza : dzb;
-    const float4* w = reinterpret_cast<const float4*>(swg + j * 64 + part * 16);
+    for (int i = 0; i < NV; ++i) x1[i] = hround((x[i] - mean) * rstd * gm[i] + x1[i]);
+    // gate: gate = ga (gb c - 1) + 2
+    float za[N], zb[N];
+    gate_z<N>(a.g, swg, x1, lane, za, zb);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float4 t = w[i];
-      dx[4 * i] += t.x * dz;
-      dx[4 * i + 1] += t.y * dz;
-      dx[4 * i + 2] += t.z * dz;
-      dx[4 * i + 3] += t.w * dz;
-    }
-  }
-  if (kLora) {
-    const uint64_t sq = a.dq.thr ? attn_seed(a.dq.seed_dev, a.dq.salt) : 0;
-    const uint64_t sv = a.dv.thr ? attn_seed(a.dv.seed_dev, a.dv.salt) : 0;
-    if (a.xd) {  // the dropped LN output of each adapter (optional; first, so that x1 dies here)
+    for (int c = 0; c < N; ++c) {
+      const float ga = sigmoidf_(za[c]), gb = sigmoidf_(zb[c]);
+      const float gc = a.g.gconst[head0 + 4 * c];
+      const float dza = dg[c] * (gb * gc - 1.0f) * ga * (1.0f - ga);
+      const float dzb = dg[c] * ga * gc * gb * (1.0f - gb);
 #pragma unroll
-      for (int which = 0; which < 2; ++which) {
-        const Drop& dd = which ? a.dv : a.dq;
-        const uint64_t sd = which ? sv : sq;
-        float xm[WL_VPL];
-#pragma unroll
-        for (int i = 0; i < WL_VPL; ++i) xm[i] = x1[i] * drop_scale(dd, sd, (uint64_t)m * WL_E + e0 + i);
-        store16_bf(a.xd + (which * a.M + m) * WL_E + e0, xm);
+      for (int j = 0; j < 8; ++j) {
+        const float dz = j < 4 ? dza : dzb;
+        const float4 t = *reinterpret_cast<const float4*>(swg + j * 64 + d0);
+        dx[4 * c] += t.x * dz;
+        dx[4 * c + 1] += t.y * dz;
+        dx[4 * c + 2] += t.z * dz;
+        dx[4 * c + 3] += t.w * dz;
       }
     }
-    // the 2r down-projection gradients of this row, packed in k pairs (one 32-byte broadcast read); the term
-    // sum_k A[k][e] da[k] of each element e as packed dot products over k pairs: the two A rows k, k + 1 read as
-    // before (32 contiguous bytes per lane, conflict-free), their 16-bit halves regrouped per element
-    const uint4 dap[2] = {*reinterpret_cast<const uint4*>(a.dx1 + m * a.ldx + WL_E),
-                          *reinterpret_cast<const uint4*>(a.dx1 + m * a.ldx + WL_E + 8)};
+    if (kLora) {
+      const uint64_t sq = a.dq.thr ? attn_seed(a.dq.seed_dev, a.dq.salt) : 0;
+      const uint64_t sv = a.dv.thr ? attn_seed(a.dv.seed_dev, a.dv.salt) : 0;
+      if (a.xd) {  // the dropped LN output of each adapter (optional; first, so that x1 dies here)
 #pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      float acc[WL_VPL];
+        for (int which = 0; which < 2; ++which) {
+          const Drop& dd = which ? a.dv : a.dq;
+          const uint64_t sd = which ? sv : sq;
+          float xm[NV];
 #pragma unroll
-      for (int i = 0; i < WL_VPL; ++i) acc[i] = 0.f;
-      const uint32_t dk[4] = {dap[which].x, dap[which].y, dap[which].z, dap[which].w};
-#pragma unroll
-      for (int kp = 0; kp < WL_R2 / 4; ++kp) {
-        const int k = which * (WL_R2 / 2) + 2 * kp;
-        const uint4* ra = reinterpret_cast<const uint4*>(sA + k * WL_E + e0);
-        const uint4* rb = reinterpret_cast<const uint4*>(sA + (k + 1) * WL_E + e0);
-        const uint4 a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
-        const uint32_t wa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        const uint32_t wb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int j = 0; j < WL_VPL / 2; ++j) {
-          // v_perm_b32 (selector bytes 0-3: the second operand's bytes, 4-7: the first's)
-          const uint32_t ev = __builtin_amdgcn_perm(wb[j], wa[j], 0x05040100u);   // (A[k][2j], A[k + 1][2j])
-          const uint32_t od = __builtin_amdgcn_perm(wb[j], wa[j], 0x07060302u);   // (A[k][2j + 1], A[k + 1][2j + 1])
-          acc[2 * j] = hdot2(ev, dk[kp], acc[2 * j]);
-          acc[2 * j + 1] = hdot2(od, dk[kp], acc[2 * j + 1]);
+          for (int i = 0; i < NV; ++i) xm[i] = x1[i] * drop_scale(dd, sd, (uint64_t)m * WL_E + e0 + wl_elem(i));
+          store_chunks_h<N>(a.xd + (which * a.M + m) * WL_E + e0, xm);
         }
       }
-      const Drop& dd = which ? a.dv : a.dq;
-      const uint64_t sd = which ? sv : sq;
+      // the 2r down-projection gradients of this row, packed in k pairs (one 32-byte broadcast read); the term
+      // sum_k A[k][e] da[k] of each element e as packed dot products over k pairs: the two A rows k, k + 1 read at the
+      // lane's elements (8 contiguous bytes per lane and chunk, conflict-free), their 16-bit halves regrouped per
+      // element
+      const uint4 dap[2] = {*reinterpret_cast<const uint4*>(a.dx1 + m * a.ldx + WL_E),
+                            *reinterpret_cast<const uint4*>(a.dx1 + m * a.ldx + WL_E + 8)};
 #pragma unroll
-      for (int i = 0; i < WL_VPL; ++i) dx[i] += acc[i] * drop_scale(dd, sd, (uint64_t)m * WL_E + e0 + i);
+      for (int which = 0; which < 2; ++which) {
+        float acc[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) acc[i] = 0.f;
+        const uint32_t dk[4] = {dap[which].x, dap[which].y, dap[which].z, dap[which].w};
+#pragma unroll
+        for (int kp = 0; kp < WL_R2 / 4; ++kp) {
+          const int k = which * (WL_R2 / 2) + 2 * kp;
+#pragma unroll
+          for (int c = 0; c < N; ++c) {
+            const uint2 ra = *reinterpret_cast<const uint2*>(sA + k * WL_E + e0 + c * WL_CHUNK);
+            const uint2 rb = *reinterpret_cast<const uint2*>(sA + (k + 1) * WL_E + e0 + c * WL_CHUNK);
+            const uint32_t wa[2] = {ra.x, ra.y}, wb[2] = {rb.x, rb.y};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              // v_perm_b32 (selector bytes 0-3: the second operand's bytes, 4-7: the first's)
+              const uint32_t ev = __builtin_amdgcn_perm(wb[j], wa[j], 0x05040100u);   // (A[k][2j], A[k + 1][2j])
+              const uint32_t od = __builtin_amdgcn_perm(wb[j], wa[j], 0x07060302u);   // (A[k][2j + 1], A[k + 1][2j + 1])
+              acc[4 * c + 2 * j] = hdot2(ev, dk[kp], acc[4 * c + 2 * j]);
+              acc[4 * c + 2 * j + 1] = hdot2(od, dk[kp], acc[4 * c + 2 * j + 1]);
+            }
+          }
+        }
+        const Drop& dd = which ? a.dv : a.dq;
+        const uint64_t sd = which ? sv : sq;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) dx[i] += acc[i] * drop_scale(dd, sd, (uint64_t)m * WL_E + e0 + wl_elem(i));
+      }
     }
-  }
-  float o[WL_VPL];
-  ln_bwd_row(dx, x, mean, rstd, gm, o);
+  } else {
 #pragma unroll
-  for (int i = 0; i < WL_VPL; ++i) o[i] += r[i];
+    for (int i = 0; i < NV; ++i) dx[i] = x[i] = gm[i] = 0.f;
+  }
+  float o[NV];
+  ln_bwd_row<W>(dx, x, mean, rstd, gm, o, sred[row], w, lane);
+  if (!live) return;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) o[i] += r[i];
   if (a.sg) {
     const float pw = a.sw[0];
 #pragma unroll
-    for (int i = 0; i < WL_VPL; ++i) o[i] = fmaf(pw, sgv[i], o[i]);
+    for (int i = 0; i < NV; ++i) o[i] = fmaf(pw, sgv[i], o[i]);
   }
-  store16(a.dh + m * WL_E + e0, o);
+  store_chunks<N>(a.dh + m * WL_E + e0, o);
   if (a.ddrop) {
 #pragma unroll
-    for (int i = 0; i < WL_VPL; ++i)
-      o[i] *= a.dprev.thr ? drop_scale(a.dprev, sp, (uint64_t)m * WL_E + e0 + i) : 1.0f;
-    store16_bf(a.ddrop + m * WL_E + e0, o);
+    for (int i = 0; i < NV; ++i)
+      o[i] *= a.dprev.thr ? drop_scale(a.dprev, sp, (uint64_t)m * WL_E + e0 + wl_elem(i)) : 1.0f;
+    store_chunks_h<N>(a.ddrop + m * WL_E + e0, o);
   }
 }
+
 
 // LoRA weight gradients of one layer, ACCUMULATED into the fp32 .grad buffers:
 //   dB_q[e, k] += s sum_m dq[m, e] a_q[m, k]        dA_q[k, e] += sum_m da_q[m, k] drop_q(x1)[m, e]
@@ -787,18 +871,63 @@ static Drop mk_drop(const int64_t* seed_dev, int salt, float p) {
   return d;
 }
 
-static int blocks_rows(int64_t M) { return (int)((M + 3) / 4); }
-static int blocks_ln1(int64_t M) { return (int)((M + WL_LN1_ROWS - 1) / WL_LN1_ROWS); }
+// ---- Launch geometry of the four row kernels: (waves per row, rows per workgroup) ------------------------------------
+// Chosen per kernel by M: below WL_ROWS_SMALL_M the adversarial passes (B = 8, M = 1608: 1.6 one-wave rows per SIMD,
+// latency-bound), from it on the clean passes (B = 32, M = 6432). The table is the A/B of tools/bench_wl.py --waves
+// (profiles/r09_bench_wl_waves.jsonl): two waves per row, two rows per workgroup everywhere but the small LN1 forward
+// (four waves, one row). The LoRA-active LN1 kernels stay at one wave per row, WL_LN1_ROWS rows: no other geometry
+// measured faster, and their 34 KB staging per row stays what it was. WL_GEOS_* list what each kernel is
+// instantiated at: its table entries and (1, 4), the one-wave form (the LoRA-active kernels' geometry, and the form the
+// tests hold the others against).
+struct WlGeo {
+  int w, r;
+};
+enum { WL_K_LN1_FWD = 0, WL_K_ADD_LN = 1, WL_K_LN_BWD = 2, WL_K_LN1_BWD = 3 };
+#ifndef WL_ROWS_SMALL_M
+#define WL_ROWS_SMALL_M 4096
+#endif
+#ifndef WL_GEO_TABLE_DEF
+#define WL_GEO_TABLE_DEF {{{4, 1}, {2, 2}}, {{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}}
+#endif
+static const WlGeo kWlGeo[4][2] = WL_GEO_TABLE_DEF;   // [kernel][M >= WL_ROWS_SMALL_M]
+#define WL_GEOS_LN1_FWD(X) X(1, 4) X(2, 2) X(4, 1)
+#define WL_GEOS(X) X(1, 4) X(2, 2)   // add + LN forward, LN backward, LN1 backward
+#define WL_GEOS_LORA(X) X(1, 4)
+static_assert(WL_LN1_ROWS == 4, "WL_GEOS_LORA holds (1, WL_LN1_ROWS)");
 
-static int ln1_fwd_launch(const Ln1Args& a, bool lora, void* stream) {
-  const int64_t M = a.M;
-  if (lora)
-    hipLaunchKernelGGL(wl_ln1_fwd_kernel<true>, dim3(blocks_ln1(M)), dim3(WL_LN1_THREADS), 0, as_stream(stream), a);
-  else
-    hipLaunchKernelGGL(wl_ln1_fwd_kernel<false>, dim3(blocks_ln1(M)), dim3(WL_LN1_THREADS), 0, as_stream(stream), a);
+static WlGeo g_wl_force = {0, 0};   // rdx_wl_rows_override (measurement and tests): w = 0 leaves the table in charge
+
+static WlGeo wl_geo(int kernel, int64_t M, bool lora) {
+  if (g_wl_force.w) return g_wl_force;
+  return lora ? WlGeo{1, WL_LN1_ROWS} : kWlGeo[kernel][M >= WL_ROWS_SMALL_M ? 1 : 0];
+}
+static bool wl_geo_built(WlGeo g) {
+#define WL_X(Wv, Rv) if (g.w == Wv && g.r == Rv) return true;
+  WL_GEOS_LN1_FWD(WL_X)   // the union of the lists
+#undef WL_X
+  return false;
+}
+
+template <typename K, typename A>
+static int wl_launch(K kernel, WlGeo g, const A& a, int64_t M, void* stream) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((M + g.r - 1) / g.r)), dim3(g.w * g.r * RDX_WAVE), 0, as_stream(stream), a);
   RDX_LAUNCH_CHECK();
   return 0;
 }
+
+static int ln1_fwd_launch(const Ln1Args& a, bool lora, void* stream) {
+  const WlGeo g = wl_geo(WL_K_LN1_FWD, a.M, lora);
+#define WL_X(Wv, Rv) \
+  if (!lora && g.w == Wv && g.r == Rv) return wl_launch(wl_ln1_fwd_kernel<false, Wv, Rv>, g, a, a.M, stream);
+  WL_GEOS_LN1_FWD(WL_X)
+#undef WL_X
+#define WL_X(Wv, Rv) \
+  if (lora && g.w == Wv && g.r == Rv) return wl_launch(wl_ln1_fwd_kernel<true, Wv, Rv>, g, a, a.M, stream);
+  WL_GEOS_LORA(WL_X)
+#undef WL_X
+  return RDX_EINVAL;
+}
+
 
 
 extern "C" {
@@ -842,8 +971,28 @@ int rdx_wl_add_ln_fwd(const float* h, const void* delta, const int64_t* seed_dev
   RDX_REQUIRE(h && delta && h2 && gamma && beta && x && mean && rstd && M > 0 && E == WL_E);
   AddLnArgs a{h, reinterpret_cast<const hst*>(delta), mk_drop(seed_dev, salt, p), h2, gamma, beta, eps,
               reinterpret_cast<hst*>(x), mean, rstd, M};
-  hipLaunchKernelGGL(wl_add_ln_fwd_kernel, dim3(blocks_rows(M)), dim3(256), 0, as_stream(stream), a);
-  RDX_LAUNCH_CHECK();
+  const WlGeo g = wl_geo(WL_K_ADD_LN, M, false);
+#define WL_X(Wv, Rv) if (g.w == Wv && g.r == Rv) return wl_launch(wl_add_ln_fwd_kernel<Wv, Rv>, g, a, M, stream);
+  WL_GEOS(WL_X)
+#undef WL_X
+  return RDX_EINVAL;
+}
+
+int rdx_wl_rows_override(int waves, int rows) {
+  if (waves == 0 && rows == 0) {
+    g_wl_force = WlGeo{0, 0};
+    return 0;
+  }
+  RDX_REQUIRE(wl_geo_built(WlGeo{waves, rows}));
+  g_wl_force = WlGeo{waves, rows};
+  return 0;
+}
+
+int rdx_wl_rows_policy(int kernel, int64_t M, int lora, int* waves, int* rows) {
+  RDX_REQUIRE(kernel >= 0 && kernel < 4 && M > 0 && waves && rows);
+  const WlGeo g = wl_geo(kernel, M, lora != 0);
+  *waves = g.w;
+  *rows = g.r;
   return 0;
 }
 
@@ -885,9 +1034,11 @@ int rdx_wl_ln_bwd(const void* dx, int64_t ldd, const float* h, const float* mean
   RDX_REQUIRE(dx && h && mean && rstd && gamma && dh && M > 0 && E == WL_E && ldd >= E && ldd % 8 == 0);
   LnBwdArgs a{reinterpret_cast<const hst*>(dx), ldd, h, mean, rstd, gamma, dres, dh,
               mk_drop(seed_dev, salt, p), reinterpret_cast<hst*>(ddrop), M};
-  hipLaunchKernelGGL(wl_ln_bwd_kernel, dim3(blocks_rows(M)), dim3(256), 0, as_stream(stream), a);
-  RDX_LAUNCH_CHECK();
-  return 0;
+  const WlGeo g = wl_geo(WL_K_LN_BWD, M, false);
+#define WL_X(Wv, Rv) if (g.w == Wv && g.r == Rv) return wl_launch(wl_ln_bwd_kernel<Wv, Rv>, g, a, M, stream);
+  WL_GEOS(WL_X)
+#undef WL_X
+  return RDX_EINVAL;
 }
 
 int rdx_wl_ln1_bwd_ex(const void* dx1, int64_t ldx, const float* dgate, const float* h, const float* mean,
@@ -906,12 +1057,16 @@ int rdx_wl_ln1_bwd_ex(const void* dx1, int64_t ldx, const float* dgate, const fl
                mk_drop(seed_dev, salt_q, p_lora), mk_drop(seed_dev, salt_v, p_lora),
                dres, dh, reinterpret_cast<hst*>(xd), M, state_grad, state_weight,
                mk_drop(seed_dev, salt_prev, p_prev), reinterpret_cast<hst*>(ddrop_prev)};
-  if (lora)
-    hipLaunchKernelGGL(wl_ln1_bwd_kernel<true>, dim3(blocks_ln1(M)), dim3(WL_LN1_THREADS), 0, as_stream(stream), a);
-  else
-    hipLaunchKernelGGL(wl_ln1_bwd_kernel<false>, dim3(blocks_ln1(M)), dim3(WL_LN1_THREADS), 0, as_stream(stream), a);
-  RDX_LAUNCH_CHECK();
-  return 0;
+  const WlGeo g = wl_geo(WL_K_LN1_BWD, M, lora);
+#define WL_X(Wv, Rv) \
+  if (!lora && g.w == Wv && g.r == Rv) return wl_launch(wl_ln1_bwd_kernel<false, Wv, Rv>, g, a, M, stream);
+  WL_GEOS(WL_X)
+#undef WL_X
+#define WL_X(Wv, Rv) \
+  if (lora && g.w == Wv && g.r == Rv) return wl_launch(wl_ln1_bwd_kernel<true, Wv, Rv>, g, a, M, stream);
+  WL_GEOS_LORA(WL_X)
+#undef WL_X
+  return RDX_EINVAL;
 }
 
 int rdx_wl_ln1_bwd(const void* dx1, int64_t ldx, const float* dgate, const float* h, const float* mean,

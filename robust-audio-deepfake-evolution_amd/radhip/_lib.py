@@ -201,6 +201,8 @@ SIGNATURES = {
                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "rdx_wl_lora_pack": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_int,
                          c_f32, c_int, c_vp]),
+    "rdx_wl_rows_policy": (c_int, [c_int, c_i64, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "rdx_wl_rows_override": (c_int, [c_int, c_int]),
     "rdx_timestamp_acc": (c_int, [c_vp, c_int, c_vp]),
     "rdx_wallclock_khz": (c_int, [c_int]),
     "rdx_focal_mixup_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_int,

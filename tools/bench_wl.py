@@ -3,6 +3,8 @@
 parts, next to a device copy of the same bytes (the HBM floor at that size) and the hipBLASLt GEMMs of a layer.
 
   python tools/bench_wl.py
+  python tools/bench_wl.py --waves     # the four row kernels at every (waves per row, rows per workgroup) geometry the
+                                       # library holds (rdx_wl_rows_override), one JSON line per pass size and geometry
 """
 import ctypes
 import json
@@ -31,11 +33,15 @@ def timed(fn, reps=50):
     return round(e0.elapsed_time(e1) / reps * 1e3, 2)
 
 
+GEOS = [(w, r) for w in (1, 2, 4) for r in (1, 2, 4, 8)]
+
+
 def main():
     dev = "cuda"
     E, H, r = 1024, 16, 8
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     res = {}
+    waves = "--waves" in sys.argv[1:]
     for B in (8, 32):
         M = B * 201
         o = {}
@@ -53,6 +59,55 @@ def main():
             check(lib().rdx_wl_ln1_fwd(_p(h), _p(gm), _p(bt), 1e-5, _p(wg), _p(bg), _p(gc), _p(aq) if lora else None,
                                        _p(av) if lora else None, 8, _p(seed) if sd else None, 11, 12, p, _p(x1),
                                        E + 16, _p(gate), _p(mean), _p(rstd), M, E, st), "ln1")
+        if waves:
+            # the row kernels alone, per geometry (the library answers RDX_EINVAL for one it does not hold); the
+            # flagship's forms first: LoRA bypassed (--lora-mode reference), hidden dropout 0.1
+            delta = torch.randn(M, E, device=dev).to(torch.bfloat16)
+            h2 = torch.empty(M, E, device=dev)
+            x2 = torch.empty(M, E, device=dev, dtype=torch.bfloat16)
+            dx1 = torch.randn(M, E + 16, device=dev).to(torch.bfloat16)
+            dgate, dres, dh = torch.randn(M, H, device=dev), torch.randn(M, E, device=dev), torch.empty(M, E, device=dev)
+
+            def res_ln1(lora):
+                check(lib().rdx_wl_res_ln1_fwd(_p(h), _p(delta), 5, 0.1, _p(h2), _p(gm), _p(bt), 1e-5, _p(wg), _p(bg),
+                                               _p(gc), _p(aq) if lora else None, _p(av) if lora else None, 8, _p(seed),
+                                               11, 12, 0.1, _p(x1), E + 16, _p(gate), _p(mean), _p(rstd), M, E, st), "x")
+
+            def ln1b(lora):
+                check(lib().rdx_wl_ln1_bwd_ex(_p(dx1), E + 16, _p(dgate), _p(h), _p(mean), _p(rstd), _p(gm), _p(bt),
+                                              _p(wg), _p(bg), _p(gc), _p(aq) if lora else None, _p(av) if lora else None,
+                                              8, _p(seed), 11, 12, 0.1, _p(dres), _p(dh), None, None, None, 7, 0.1,
+                                              _p(x2), M, E, st), "x")
+            kern = {
+                "res_ln1_fwd_nolora": lambda: res_ln1(False),
+                "add_ln_fwd_p0.1": lambda: check(lib().rdx_wl_add_ln_fwd(
+                    _p(h), _p(delta), _p(seed), 3, 0.1, _p(h2), _p(gm), _p(bt), 1e-5, _p(x2), _p(mean), _p(rstd), M, E,
+                    st), "x"),
+                "ln_bwd_p0.1": lambda: check(lib().rdx_wl_ln_bwd(
+                    _p(dx1), E + 16, _p(h), _p(mean), _p(rstd), _p(gm), _p(dres), _p(dh), _p(seed), 3, 0.1, _p(x2), M, E,
+                    st), "x"),
+                "ln1_bwd_nolora_ddrop": lambda: ln1b(False),
+                "res_ln1_fwd_lora": lambda: res_ln1(True),
+                "ln1_bwd_lora_ddrop": lambda: ln1b(True),
+            }
+            ln1(False, 0.0, False)     # mean / rstd of h for the backward kernels
+            for gw, gr in GEOS:
+                if lib().rdx_wl_rows_override(gw, gr) != 0:
+                    continue
+                try:
+                    row = {"B": B, "M": M, "waves": gw, "rows": gr}
+                    for rep in range(2):      # twice: the spread of a reading
+                        for name, fn in kern.items():
+                            if name in row and row[name] is None:
+                                continue
+                            try:
+                                row.setdefault(name, []).append(timed(fn, reps=200))
+                            except RuntimeError:      # the LoRA-active kernels hold fewer geometries
+                                row[name] = None
+                finally:
+                    check(lib().rdx_wl_rows_override(0, 0), "rows_override")
+                print(json.dumps(row), flush=True)
+            continue
         o["copy_h_fp32"] = timed(lambda: h.clone())
         o["ln1_fwd_lora_p0.1"] = timed(lambda: ln1(True, 0.1))
         o["ln1_fwd_lora_p0"] = timed(lambda: ln1(True, 0.0, False))

@@ -44,10 +44,16 @@ def main():
     ap.add_argument("--before", default=None,
                     help="end the window at the first launch whose name contains this (bench.py: 'ts_acc_kernel', "
                          "the first clock stamp of the kernel-timing replay, so the window is the timed region)")
+    ap.add_argument("--split", default=None,
+                    help="comma-separated name fragments: list the matching kernels once more, split by launch size "
+                         "(workgroups x threads), e.g. the row kernels of csrc/wavlm_layer.hip by pass size")
     a = ap.parse_args()
     op = gzip.open if a.trace.endswith(".gz") else open
     with op(a.trace, "rt") as f:
-        rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(f)]
+        rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"],
+                 (int(r.get("Grid_Size") or r.get("Grid_Size_X") or 0), int(r.get("Workgroup_Size") or
+                                                                           r.get("Workgroup_Size_X") or 0)))
+                for r in csv.DictReader(f)]
     rows.sort()
     if a.before:
         # the timed region precedes the stamped kernel-timing replay; warm-up and capture precede both
@@ -72,7 +78,7 @@ def main():
     per = defaultdict(lambda: [0, 0])
     cat = defaultdict(float)
     busy = 0
-    for s, e, n in win:
+    for s, e, n, _ in win:
         short = re.sub(r"\(.*", "", n)[:100]
         if "at::native::" in n and len(short) < 40:   # a templated name cut at its first parenthesis
             short = n[:160]
@@ -83,7 +89,7 @@ def main():
     m = a.micro
     # time with at least one kernel running (concurrent branches overlap: the kernel sum can exceed the wall)
     union, cur_s, cur_e = 0, None, None
-    for s, e, _ in win:
+    for s, e, _, _ in win:
         if cur_e is None or s > cur_e:
             if cur_e is not None:
                 union += cur_e - cur_s
@@ -101,6 +107,20 @@ def main():
     print(f"# top {a.top} kernels (ms per micro-batch, launches per micro-batch, avg us)")
     for k, (c, t) in sorted(per.items(), key=lambda kv: -kv[1][1])[:a.top]:
         print(f"{1e-6 * t / m:9.3f} {c / m:8.1f} {1e-3 * t / c:10.2f}  {k}")
+    if a.split:
+        frags = a.split.split(",")
+        by = defaultdict(lambda: [0, 0])
+        for s, e, n, (grid, wg) in win:
+            if any(f in n for f in frags):
+                k = (re.sub(r"\(.*", "", n)[:100], grid // wg if wg else 0, wg)
+                by[k][0] += 1
+                by[k][1] += e - s
+        print("# split by launch size (ms per micro-batch, launches per micro-batch, avg us, workgroups x threads)")
+        tot = 0
+        for (k, nwg, wg), (c, t) in sorted(by.items()):
+            tot += t
+            print(f"{1e-6 * t / m:9.3f} {c / m:8.1f} {1e-3 * t / c:10.2f}  {nwg:6d} x {wg:4d}  {k}")
+        print(f"{1e-6 * tot / m:9.3f} total of the split kernels")
     print("# radhip kernels")
     for k, (c, t) in sorted(per.items(), key=lambda kv: -kv[1][1]):
         if categorize(k) == "radhip (hand-written HIP)":
