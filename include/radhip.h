@@ -229,6 +229,29 @@ int rdx_pad_mixup(const float* sig, const int64_t* offsets, const int64_t* lens,
                   float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Whole-recording scoring (radhip/recordings.py; no reference counterpart: the reference scores the
+ * first max_len samples of a file and drops the rest).
+ * rdx_window_gather: model inputs [nwin, win] cut from packed recordings by a window table,
+ *   out[w][i] = sig[ offsets[r] + (lens[r] <= win ? i mod lens[r] : start[w] + i) ],  r = rec[w]
+ * i.e. a recording no longer than a window is filled as pad (src/data_utils.py:107-113) fills it, a
+ * longer one is cut at start[w]. Unlike rdx_pad_mixup a recording may own any number of windows,
+ * in any order. offsets / lens (per recording) and rec / start (per window) are host arrays; sig
+ * is fp32 at arbitrary element offsets; out is 16-byte aligned; win % 4 == 0 (else
+ * RDX_EUNSUPPORTED); start[w] + win <= lens[r] when lens[r] > win, start[w] == 0 otherwise. The
+ * caller vouches that rec[w] indexes offsets / lens and that every recording lies inside sig.
+ * rdx_segment_reduce: per segment r of scores[seg[r] .. seg[r + 1]) (seg: nseg + 1 int64 prefix
+ * offsets in DEVICE memory, every segment non-empty): mean (fp32 two-sum accumulation in a fixed
+ * order, rounded once: within (n - 1) 2^-24 max|s| of the exact mean of n scores), exact min and
+ * max, and argmin = the first index inside the segment that attains the minimum. One wave per
+ * segment, no atomics: two launches give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+int rdx_window_gather(const float* sig, const int64_t* offsets, const int64_t* lens,
+                      const int64_t* rec, const int64_t* start, int nwin, int64_t win, float* out,
+                      void* stream);
+int rdx_segment_reduce(const float* scores, const int64_t* seg, int nseg, float* out_mean,
+                       float* out_min, float* out_max, int64_t* out_argmin, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * FGM attack, replaces FGM.attack (src/main.py:85-94): for each tensor i,
  *   backup_i = p_i;  if (||g_i|| != 0 && !isnan(||g_i||))  p_i += eps * g_i / ||g_i||
  * Host arrays of ntensors (<= 32) device pointers, fp32. workspace: fp64 [ntensors * 256].

@@ -13,7 +13,8 @@ Same flags, config keys and output layout as the reference (src/main.py:161-796,
       {eval_output}, t-DCF_EER.txt, eval_scores_2021DF.txt + t-DCF_EER_2021DF.txt (auto_eval_2021_df)
 Extra flags: --amp {fp16,bf16,fp32} (default fp16: the reference's fp16 autocast + GradScaler, on the kernels of
 libradhip_f16.so; bf16 runs the same kernels with bf16 storage, no GradScaler), --eager (no HIP graphs),
---loader-threads.
+--loader-threads; --score_files LIST [--score_hop N] [--score_reduce {mean,min,max}] [--score_timeline] scores whole
+recordings of any length with --eval_model_weights and writes recording_scores.txt (radhip/recordings.py).
 
 Differences, all documented in DESIGN.md:
   * data-parallel: one process per GPU (RCCL); the train list is sharded per global micro-step; by default
@@ -291,6 +292,28 @@ class Runner:
         self.log("DONE.")
         self.tdcf(self.eval_score_path, self.tag / "loaded_model_t-DCF_EER.txt")
 
+    def run_score_files(self, model):
+        """--score_files: whole recordings of any length, windowed and reduced on the GPU (radhip/recordings.py).
+        Both files are written after every recording has been scored, so a bad file leaves nothing partial."""
+        from radhip.recordings import RecordingScorer, write_scores, write_timeline
+        args = self.args
+        if self.world > 1:
+            raise RuntimeError("--score_files scores on one GPU: run it without torch.distributed.run")
+        load_weights(model, args.eval_model_weights, self.device, strict=True)
+        self.log("Model loaded : {}".format(args.eval_model_weights))
+        load_criterion(self.criterion, args.eval_model_weights, self.log)
+        with open(args.score_files) as f:
+            paths = [ln.strip() for ln in f if ln.strip()]
+        self.log(f"no. recordings: {len(paths)}")
+        bs = int(self.config.get("test_config", {}).get("batch_size", self.config["batch_size"]))
+        scorer = RecordingScorer(model, self.device, criterion=self.criterion, amp=args.eval_amp, batch_size=bs,
+                                 hop=args.score_hop, reduce=args.score_reduce, threads=self.threads)
+        records = scorer.score(paths, timeline=args.score_timeline)
+        write_scores(self.tag / "recording_scores.txt", records)
+        if args.score_timeline:
+            write_timeline(self.tag / "recording_timeline.txt", records)
+        self.log("Scores saved to {}".format(self.tag / "recording_scores.txt"))
+
     # ------------------------------------------------------------------ train ------------------
     def make_stepper(self, trainer, B):
         """How micro-batches execute: the accumulation window (HIP graphs, radhip/window.py), the
@@ -380,6 +403,9 @@ class Runner:
         for given in (args.pretrained_weights, args.resume):      # (a full train state carries the criterion itself)
             if given and not (given == args.resume and self.resume_state is not None):
                 load_criterion(self.criterion, given, self.log)
+        if args.score_files:
+            self.run_score_files(model)
+            return
         if args.eval:
             self.run_eval(model)
             return
@@ -599,7 +625,24 @@ def parse_args(argv=None):
     parser.add_argument("--exact_rawboost", action="store_true",
                         help="draw the RawBoost ISD / SSI noise with the reference's numpy calls (randn / choice per "
                              "sample) instead of one Philox seed per call")
-    return parser.parse_args(argv)
+    parser.add_argument("--score_files", type=str, default=None, metavar="LIST",
+                        help="score whole recordings of any length and exit: LIST holds one mono 16 kHz .flac path per "
+                             "line; every recording is covered by 64600-sample windows (radhip/recordings.py), scored "
+                             "with --eval_model_weights at --eval_amp, and written to recording_scores.txt as "
+                             "'path n_samples n_windows score min max argmin_start'")
+    parser.add_argument("--score_hop", type=int, default=32300, metavar="N",
+                        help="samples between window starts of a recording longer than one window (1..64600)")
+    parser.add_argument("--score_reduce", default="mean", choices=["mean", "min", "max"],
+                        help="the window statistic written as a recording's score")
+    parser.add_argument("--score_timeline", action="store_true",
+                        help="also write recording_timeline.txt: one 'path start score' line per window")
+    args = parser.parse_args(argv)
+    if args.score_files is not None:
+        if args.eval_model_weights is None:
+            parser.error("--score_files requires --eval_model_weights")
+        if not 1 <= args.score_hop <= 64600:
+            parser.error("--score_hop must lie in 1..64600")
+    return args
 
 
 def main(args):

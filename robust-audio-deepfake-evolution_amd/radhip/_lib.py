@@ -92,6 +92,8 @@ SIGNATURES = {
     "rdx_resample_batch": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(ResampleJob), c_int, c_vp]),
     "rdx_pad_mixup": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_int,
                               c_i64, ctypes.POINTER(c_int), c_f32, c_vp, c_vp]),
+    "rdx_window_gather": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 4 + [c_int, c_i64, c_vp, c_vp]),
+    "rdx_segment_reduce": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rdx_bnselu_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_bnselu_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_res_tail_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

@@ -6,6 +6,7 @@ path. Tensors must live on a ROCm device.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -845,6 +846,54 @@ def pad_mixup(sig_flat, offsets, lens, starts, max_len, perm=None, lam=1.0, out=
     check(lib().rdx_pad_mixup(_p(sig_flat), I64(*offsets), I64(*lens), I64(*starts), n, int(max_len), pa, float(lam),
                               _p(out), _stream(sig_flat)), "pad_mixup")
     return out
+
+
+def _i64(a):
+    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def window_gather(sig_flat, offsets, lens, rec, start, win, out=None):
+    """[nwin, win] model inputs cut from packed recordings: window w is recording rec[w] from sample start[w], or the
+    whole recording tiled when it is no longer than win (rdx_window_gather; radhip.recordings.window_table makes
+    the table). offsets / lens per recording, rec / start per window: host integer sequences."""
+    _require_gpu(sig_flat)
+    if sig_flat.dtype != torch.float32 or not sig_flat.is_contiguous():
+        raise TypeError("window_gather: sig must be a contiguous float32 tensor")
+    (offsets, po), (lens, pl), (rec, pr), (start, ps) = _i64(offsets), _i64(lens), _i64(rec), _i64(start)
+    nwin, win = rec.size, int(win)
+    if offsets.size != lens.size or start.size != nwin:
+        raise ValueError("window_gather: offsets / lens and rec / start must pair up")
+    if nwin and (rec.min() < 0 or rec.max() >= lens.size):
+        raise ValueError("window_gather: rec names a recording outside the table")
+    if lens.size and (offsets.min() < 0 or lens.min() <= 0 or (offsets + lens).max() > sig_flat.numel()):
+        raise ValueError(f"window_gather: a recording lies outside the {sig_flat.numel()}-sample buffer")
+    if out is None:
+        out = torch.empty(nwin, win, device=sig_flat.device, dtype=torch.float32)
+    if out.shape != (nwin, win) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"window_gather: out must be a contiguous float32 [{nwin}, {win}] device tensor")
+    check(lib().rdx_window_gather(_p(sig_flat), po, pl, pr, ps, nwin, win, _p(out), _stream(sig_flat)),
+          "window_gather")
+    return out
+
+
+def segment_reduce(scores, seg):
+    """(mean, min, max [fp32 n], argmin [int64 n]) of scores[seg[r]:seg[r + 1]] for the n = len(seg) - 1 non-empty
+    segments, on the device (rdx_segment_reduce): fixed accumulation order, argmin = the first index inside the
+    segment that attains the minimum. seg: host integer prefix offsets."""
+    _require_gpu(scores)
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise TypeError("segment_reduce: scores must be a contiguous float32 tensor")
+    seg, _ = _i64(seg)
+    n = seg.size - 1
+    if n < 1 or seg[0] < 0 or seg[-1] > scores.numel() or (seg[1:] <= seg[:-1]).any():
+        raise ValueError("segment_reduce: seg must be increasing prefix offsets inside scores (no empty segment)")
+    seg_dev = torch.from_numpy(seg).to(scores.device)
+    f = torch.empty(3, n, device=scores.device, dtype=torch.float32)
+    arg = torch.empty(n, device=scores.device, dtype=torch.int64)
+    check(lib().rdx_segment_reduce(_p(scores), _p(seg_dev), n, _p(f[0]), _p(f[1]), _p(f[2]), _p(arg),
+                                   _stream(scores)), "segment_reduce")
+    return f[0], f[1], f[2], arg
 
 
 # -------------------------------------------------------- SincNet residual stack (NHWC) -------

@@ -1,0 +1,213 @@
+"""Scoring whole recordings of any length: "which of these files are spoofed, and where?".
+
+The trial-list scorer (radhip/infer.py, radhip/data.py) feeds the model the reference's `pad` of every file: its first
+64 600 samples, or the file tiled to that length. Here a recording is covered by windows of 64 600 samples instead,
+every window is scored by the unchanged model forward, and the window scores are reduced to one record per recording.
+
+The window rule (`window_table`, the only statement of it):
+  * len <= win: one window at start 0, filled as `pad` fills it (head crop at len == win, else x[i % len]), so a file
+    of ASVspoof length gets exactly the samples the eval path feeds the model;
+  * len >  win: n = 1 + ceil((len - win) / hop) windows, starts k * hop for k < n - 1 and len - win for the last,
+    which therefore ends flush with the recording. Every sample lies in a window; nothing is tiled or zero-padded;
+  * len == 0: an error that names the recording.
+
+Data path: recordings are decoded by the native batch reader into one packed pinned buffer (radhip.audio.read_batch),
+uploaded in one copy, cut into model inputs on the device by rdx_window_gather, scored through radhip.infer._scores
+and reduced on the device by rdx_segment_reduce (csrc/recwin.hip). There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from . import audio
+from .data import CUT, _PinnedBuf
+from .infer import _scores
+from .ops import segment_reduce, window_gather
+
+SAMPLE_RATE = 16000
+# Packed samples resident per chunk of recordings: 2^24 fp32 samples = 64 MiB on the host (pinned) and on the device,
+# about 17 minutes of audio. A chunk always holds at least one recording, so a single longer recording is the only
+# way past the cap.
+CHUNK_SAMPLES = 1 << 24
+AMP = {None: None, "fp32": None, "x3": "x3", "bf16": torch.bfloat16, "fp16": torch.float16}
+REDUCE = ("mean", "min", "max")
+
+
+def window_table(lens, hop, win=CUT, names=None):
+    """(rec[int64 W], start[int64 W], seg[int64 n + 1]): window w covers recording rec[w] from sample start[w], and
+    recording r owns windows seg[r] .. seg[r + 1]. 1 <= hop <= win. `names` only words the zero-length error."""
+    hop, win = int(hop), int(win)
+    if win < 1 or not 1 <= hop <= win:
+        raise ValueError(f"window_table: need 1 <= hop <= win, got hop {hop}, win {win}")
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    bad = np.nonzero(lens <= 0)[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"{names[i] if names is not None else f'recording {i}'}: no samples to score "
+                         f"(length {int(lens[i])})")
+    count = np.where(lens <= win, 1, 1 - (-(lens - win) // hop))
+    seg = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(count, out=seg[1:])
+    rec = np.repeat(np.arange(lens.size, dtype=np.int64), count)
+    k = np.arange(rec.size, dtype=np.int64) - seg[rec]
+    start = np.where(lens[rec] <= win, 0, np.minimum(k * hop, lens[rec] - win)).astype(np.int64)
+    return rec, start, seg
+
+
+def window_samples(x, start, win=CUT):
+    """The numpy restatement of one window of recording x (what rdx_window_gather writes for it)."""
+    x = np.asarray(x)
+    n = x.shape[0]
+    if n <= win:
+        return x[np.arange(win) % n]
+    return x[start:start + win]
+
+
+def _chunks(lens, cap):
+    """[i0, i1) runs of recordings whose packed samples stay within cap (one recording at least)."""
+    i0, total = 0, 0
+    for i, n in enumerate(lens):
+        if i > i0 and total + n > cap:
+            yield i0, i
+            i0, total = i, 0
+        total += int(n)
+    if len(lens) > i0:
+        yield i0, len(lens)
+
+
+class RecordingScorer:
+    """One record per recording: {name, n_samples, n_windows, score, min, max, argmin_start} and, with
+    timeline=True, window_starts / window_scores. The score of a window is the bona-fide logit (or the OC-Softmax
+    cosine when `criterion` carries a centre), so `min` is the most spoof-like window and `argmin_start` the sample
+    at which it starts; `score` is the mean, min or max of the windows according to `reduce`.
+
+    The windows of all recordings, in input order, are cut into batches of `batch_size`: short and long recordings
+    share batches and only the last batch is partial. Recordings are read, uploaded and cut in chunks of at most
+    CHUNK_SAMPLES (2^24) packed samples, 64 MiB of pinned host memory and as much device memory, however long the
+    list is; a batch may straddle two chunks. What grows with the list is one fp32 score per window and the records.
+
+    amp: "x3" (default, the scorer of main.py --eval), "fp32", "bf16" or "fp16", as radhip.infer._scores takes them.
+    """
+
+    def __init__(self, model, device, criterion=None, amp="x3", batch_size=32, hop=32300, reduce="mean", win=CUT,
+                 threads=8):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("RecordingScorer runs the HIP path and needs a ROCm GPU (there is no CPU path)")
+        if amp not in AMP:
+            raise ValueError(f"amp {amp!r} is not one of {[a for a in AMP if a]}")
+        if reduce not in REDUCE:
+            raise ValueError(f"reduce {reduce!r} is not one of {list(REDUCE)}")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        window_table([1], hop, win)     # the rule's own check of hop and win
+        self.model, self.criterion, self.amp = model, criterion, AMP[amp]
+        self.B, self.hop, self.win, self.reduce, self.threads = int(batch_size), int(hop), int(win), reduce, threads
+        self.pin = _PinnedBuf()
+
+    # ------------------------------------------------------------------ inputs -----------------
+    def score(self, paths, timeline=False):
+        """paths: mono 16 kHz .flac files. A file that is not raises AudioReadError naming it before anything is
+        scored (resampling and down-mixing are not done here)."""
+        paths = [str(p) for p in paths]
+        lens = np.empty(len(paths), dtype=np.int64)
+        for i, p in enumerate(paths):
+            frames, ch, sr, _ = audio.probe(p)
+            if ch != 1:
+                raise audio.AudioReadError(f"{p}: expected a mono recording, got {ch} channels")
+            if sr != SAMPLE_RATE:
+                raise audio.AudioReadError(f"{p}: expected {SAMPLE_RATE} Hz, got {sr} Hz (resampling is not done here)")
+            if frames == 0:
+                raise audio.AudioReadError(f"{p}: STREAMINFO has no sample count")
+            lens[i] = frames
+
+        def load(i0, i1, host):
+            audio.read_batch(paths[i0:i1], out=host, threads=self.threads)
+        return self._run(paths, lens, load, timeline)
+
+    def score_arrays(self, arrays, names=None, timeline=False):
+        """arrays: 1-D float32 waveforms at 16 kHz."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+        names = [f"array {i}" for i in range(len(arrays))] if names is None else [str(n) for n in names]
+        if len(names) != len(arrays):
+            raise ValueError(f"{len(names)} names for {len(arrays)} arrays")
+        for n, a in zip(names, arrays):
+            if a.ndim != 1:
+                raise ValueError(f"{n}: expected a 1-D waveform, got shape {a.shape}")
+        lens = np.array([a.shape[0] for a in arrays], dtype=np.int64)
+
+        def load(i0, i1, host):
+            o = 0
+            for a in arrays[i0:i1]:
+                host[o:o + a.shape[0]] = torch.from_numpy(a)
+                o += a.shape[0]
+        return self._run(names, lens, load, timeline)
+
+    # ----------------------------------------------------------------- scoring -----------------
+    def _batch_scores(self, xb):
+        return _scores(self.model, xb, self.criterion, self.amp).float()
+
+    @torch.no_grad()
+    def _run(self, names, lens, load, timeline):
+        if len(names) == 0:
+            return []
+        rec, start, seg = window_table(lens, self.hop, self.win, names)
+        self.model.eval()
+        xb = torch.empty(self.B, self.win, device=self.device, dtype=torch.float32)
+        fill, parts = 0, []
+        if self.amp == "x3":
+            # as produce_evaluation_file_sharded: a pass neither starts from cached weight planes nor keeps them
+            from . import wavlm_x3
+            wavlm_x3.drop(self.model)
+        try:
+            with torch.cuda.device(self.device):
+                for i0, i1 in _chunks(lens, CHUNK_SAMPLES):
+                    total = int(lens[i0:i1].sum())
+                    load(i0, i1, self.pin.get(total))
+                    sig = self.pin.upload(total, self.device)
+                    clens = lens[i0:i1]
+                    offs = np.zeros(i1 - i0, dtype=np.int64)
+                    np.cumsum(clens[:-1], out=offs[1:])
+                    w, w1 = int(seg[i0]), int(seg[i1])
+                    while w < w1:
+                        m = min(self.B - fill, w1 - w)
+                        window_gather(sig, offs, clens, rec[w:w + m] - i0, start[w:w + m], self.win,
+                                      out=xb[fill:fill + m])
+                        w, fill = w + m, fill + m
+                        if fill == self.B:
+                            parts.append(self._batch_scores(xb))
+                            fill = 0
+                if fill:
+                    parts.append(self._batch_scores(xb[:fill]))
+        finally:
+            if self.amp == "x3":
+                wavlm_x3.drop(self.model)
+        scores = torch.cat(parts)
+        mean, lo, hi, arg = segment_reduce(scores, seg)
+        mean, lo, hi = (t.cpu().numpy().astype(np.float32).tolist() for t in (mean, lo, hi))
+        first = start[seg[:-1] + arg.cpu().numpy()].tolist()
+        pick = {"mean": mean, "min": lo, "max": hi}[self.reduce]
+        out = [{"name": names[r], "n_samples": int(lens[r]), "n_windows": int(seg[r + 1] - seg[r]), "score": pick[r],
+                "min": lo[r], "max": hi[r], "argmin_start": int(first[r])} for r in range(len(names))]
+        if timeline:
+            flat = scores.cpu().numpy().astype(np.float32).tolist()
+            for r, d in enumerate(out):
+                d["window_starts"] = start[seg[r]:seg[r + 1]].tolist()
+                d["window_scores"] = flat[int(seg[r]):int(seg[r + 1])]
+        return out
+
+
+def write_scores(path, records):
+    """One line per recording, in input order: "name n_samples n_windows score min max argmin_start". The floats are
+    written as radhip.infer._write writes a score: str() of the float32 value widened to a double."""
+    with open(path, "w") as fh:
+        for d in records:
+            fh.write("{} {} {} {} {} {} {}\n".format(d["name"], d["n_samples"], d["n_windows"], d["score"], d["min"],
+                                                     d["max"], d["argmin_start"]))
+
+
+def write_timeline(path, records):
+    """One line per window: "name start score"."""
+    with open(path, "w") as fh:
+        for d in records:
+            for st, sco in zip(d["window_starts"], d["window_scores"]):
+                fh.write("{} {} {}\n".format(d["name"], st, sco))
