@@ -252,6 +252,47 @@ int rdx_segment_reduce(const float* scores, const int64_t* seg, int nseg, float*
                        float* out_min, float* out_max, int64_t* out_argmin, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ingest for whole-recording scoring (radhip/recordings.py, convert=True; csrc/ingest.hip): recordings
+ * of any integer sample rate and channel count -> mono at new_freq, down-mixed (arithmetic mean over
+ * channels) and resampled by the filter of rdx_resample_kernel. Output length
+ * ceil(new_g * frames / orig_g); frames outside [0, frames) are zero.
+ * rdx_ingest_taps: the compact taps of that filter, on the HOST. Of the 2 * width + orig_g dense
+ *   positions of phase p only first[p] .. first[p] + cnt[p] - 1 lie inside the window
+ *   (|t| < lowpass_width; the others are cos^2(pi / 2), < 1e-30). ntap = max_p cnt[p]
+ *   (<= 2 * width + 2). first [new_g] int32; taps [ntap, new_g] fp32 TAP-MAJOR, taps[j * new_g + p] =
+ *   the value rdx_resample_kernel stores at dense position first[p] + j for j < cnt[p], 0 beyond.
+ *   first == taps == NULL: size query (ntap, width, orig_g, new_g only). taps_cap < ntap * new_g:
+ *   RDX_EINVAL. RDX_EUNSUPPORTED if first[] (continued by orig_g + first[0]) ever decreased, which the
+ *   kernel's tile relies on; no rate is known to do so.
+ * rdx_ingest_plan: the tile rdx_ingest_resample takes for one (orig_g, new_g, ntap, channels): outputs
+ *   per workgroup (a multiple of 256, <= 1024), its LDS bytes (<= 64 KiB) and whether the taps are
+ *   staged in LDS (else read from global memory). RDX_EUNSUPPORTED: channels > 1024, or a ratio
+ *   so large that the input span of 256 outputs does not fit in 64 KiB of LDS (orig_g / new_g of
+ *   about 60: source rates near 1 MHz for 16 kHz).
+ * rdx_ingest_resample: any number of jobs, one recording each: interleaved fp32 [frames, channels] at
+ *   in + in_offset -> fp32 [ceil(new_g * frames / orig_g)] at out + out_offset; first / taps are
+ *   DEVICE copies of rdx_ingest_taps' arrays, any number of rates packed, a job's at first_offset /
+ *   taps_offset. jobs is a HOST array. in_elems / out_elems / first_elems / taps_elems are the
+ *   buffers' lengths in elements: a job that reaches outside any of them, a null pointer or a
+ *   non-positive count is RDX_EINVAL; what rdx_ingest_plan refuses, or a recording of more than 2^30
+ *   workgroups, is RDX_EUNSUPPORTED. Every job is checked before the first launch. fp32 fmaf chain
+ *   in tap order, no atomics: two launches give the same bits. Floats of out that belong to no job
+ *   are not written.
+ * ------------------------------------------------------------------------------------------ */
+int rdx_ingest_taps(int orig_freq, int new_freq, int lowpass_width, double rolloff, int32_t* first,
+                    float* taps, int64_t taps_cap, int* ntap_out, int* width_out, int* orig_g_out,
+                    int* new_g_out);
+int rdx_ingest_plan(int orig_g, int new_g, int ntap, int channels, int* block_out,
+                    int* lds_bytes_out, int* taps_in_lds_out);
+typedef struct {
+  int64_t in_offset, frames, out_offset, first_offset, taps_offset;
+  int32_t channels, orig_g, new_g, ntap, width, reserved;
+} rdx_ingest_job;
+int rdx_ingest_resample(const float* in, int64_t in_elems, float* out, int64_t out_elems,
+                        const int32_t* first, int64_t first_elems, const float* taps,
+                        int64_t taps_elems, const rdx_ingest_job* jobs, int njobs, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * FGM attack, replaces FGM.attack (src/main.py:85-94): for each tensor i,
  *   backup_i = p_i;  if (||g_i|| != 0 && !isnan(||g_i||))  p_i += eps * g_i / ||g_i||
  * Host arrays of ntensors (<= 32) device pointers, fp32. workspace: fp64 [ntensors * 256].

@@ -20,7 +20,8 @@ enum {
   RDX_IO_ECORRUPT = -103,  /* bad frame header, subframe, CRC-8/CRC-16, or sample count != STREAMINFO */
   RDX_IO_ESHORT = -104,    /* decoded more frames than the capacity given (frames_out holds the count) */
   RDX_IO_ECHANNELS = -105, /* batch loader: file is not mono */
-  RDX_IO_EARG = -106
+  RDX_IO_EARG = -106,
+  RDX_IO_ECHCOUNT = -107   /* interleaved batch loader: channel count differs from channels[i] */
 };
 
 const char* rdx_io_strerror(int code);
@@ -39,6 +40,8 @@ int rdx_flac_decode_mem(const uint8_t* data, int64_t nbytes, double* out, int64_
  * the return value is the first failing status (0 if all succeeded). */
 int rdx_flac_read_batch(const char* const* paths, int n, float* out, const int64_t* offsets,
                         const int64_t* caps, int64_t* frames_out, int* status, int threads);
+
+/* The multi-channel batch loader of the ingest stage is declared in radio_interleaved.h. */
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "../../include/radio.h"
+#include "../../include/radio_interleaved.h"
 
 namespace {
 
@@ -383,6 +384,40 @@ int rdx_flac_read_batch(const char* const* paths, int n, float* out, const int64
   return 0;
 }
 
+int rdx_flac_read_batch_interleaved(const char* const* paths, int n, float* out, const int64_t* offsets,
+                                    const int64_t* caps, const int* channels, int64_t* frames_out, int* status,
+                                    int threads) {
+  if (n < 0 || (n > 0 && (!paths || !out || !offsets || !caps || !channels || !frames_out || !status)))
+    return RDX_IO_EARG;
+  if (threads <= 0) threads = 1;
+  if (threads > n) threads = n > 0 ? n : 1;
+  std::atomic<int> next{0};
+  auto work = [&]() {
+    std::vector<uint8_t> buf;
+    while (true) {
+      int i = next.fetch_add(1);
+      if (i >= n) break;
+      frames_out[i] = 0;
+      if (!slurp(paths[i], &buf)) { status[i] = RDX_IO_ENOENT; continue; }
+      StreamInfo si;
+      if (parse_header(buf.data(), buf.size(), &si) < 0) { status[i] = RDX_IO_EFORMAT; continue; }
+      // caps[i] frames of channels[i] floats were reserved: another channel count would not fit them
+      if (si.channels != channels[i]) { status[i] = RDX_IO_ECHCOUNT; continue; }
+      int64_t r = decode<float>(buf.data(), buf.size(), out + offsets[i], caps[i], nullptr);
+      if (r < 0) { status[i] = (int)r; continue; }
+      frames_out[i] = r;
+      status[i] = r > caps[i] ? RDX_IO_ESHORT : 0;
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+  work();
+  for (auto& th : pool) th.join();
+  for (int i = 0; i < n; ++i)
+    if (status[i]) return status[i];
+  return 0;
+}
+
 const char* rdx_io_strerror(int code) {
   switch (code) {
     case 0: return "ok";
@@ -392,6 +427,7 @@ const char* rdx_io_strerror(int code) {
     case RDX_IO_ESHORT: return "output capacity smaller than the decoded length";
     case RDX_IO_ECHANNELS: return "batch loader expects mono files";
     case RDX_IO_EARG: return "invalid argument";
+    case RDX_IO_ECHCOUNT: return "channel count differs from the one the buffer was sized for";
     default: return "unknown radio error";
   }
 }

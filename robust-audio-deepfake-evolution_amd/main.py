@@ -14,7 +14,8 @@ Same flags, config keys and output layout as the reference (src/main.py:161-796,
 Extra flags: --amp {fp16,bf16,fp32} (default fp16: the reference's fp16 autocast + GradScaler, on the kernels of
 libradhip_f16.so; bf16 runs the same kernels with bf16 storage, no GradScaler), --eager (no HIP graphs),
 --loader-threads; --score_files LIST [--score_hop N] [--score_reduce {mean,min,max}] [--score_timeline] scores whole
-recordings of any length with --eval_model_weights and writes recording_scores.txt (radhip/recordings.py).
+recordings of any length with --eval_model_weights and writes recording_scores.txt (radhip/recordings.py);
+--score_convert lets LIST name .flac / .wav files of any sample rate and channel count (converted on the GPU).
 
 Differences, all documented in DESIGN.md:
   * data-parallel: one process per GPU (RCCL); the train list is sharded per global micro-step; by default
@@ -307,7 +308,8 @@ class Runner:
         self.log(f"no. recordings: {len(paths)}")
         bs = int(self.config.get("test_config", {}).get("batch_size", self.config["batch_size"]))
         scorer = RecordingScorer(model, self.device, criterion=self.criterion, amp=args.eval_amp, batch_size=bs,
-                                 hop=args.score_hop, reduce=args.score_reduce, threads=self.threads)
+                                 hop=args.score_hop, reduce=args.score_reduce, threads=self.threads,
+                                 convert=args.score_convert)
         records = scorer.score(paths, timeline=args.score_timeline)
         write_scores(self.tag / "recording_scores.txt", records)
         if args.score_timeline:
@@ -636,7 +638,13 @@ def parse_args(argv=None):
                         help="the window statistic written as a recording's score")
     parser.add_argument("--score_timeline", action="store_true",
                         help="also write recording_timeline.txt: one 'path start score' line per window")
+    parser.add_argument("--score_convert", action="store_true",
+                        help="with --score_files: accept .flac and .wav recordings of any integer sample rate and "
+                             "channel count; they are down-mixed and resampled to 16 kHz on the GPU, and n_samples, "
+                             "window starts and argmin_start are in 16 kHz samples")
     args = parser.parse_args(argv)
+    if args.score_convert and args.score_files is None:
+        parser.error("--score_convert goes with --score_files")
     if args.score_files is not None:
         if args.eval_model_weights is None:
             parser.error("--score_files requires --eval_model_weights")

@@ -58,6 +58,24 @@ class ResampleJob(ctypes.Structure):
     ]
 
 
+class IngestJob(ctypes.Structure):
+    """Mirror of rdx_ingest_job (include/radhip.h)."""
+
+    _fields_ = [
+        ("in_offset", c_i64),
+        ("frames", c_i64),
+        ("out_offset", c_i64),
+        ("first_offset", c_i64),
+        ("taps_offset", c_i64),
+        ("channels", ctypes.c_int32),
+        ("orig_g", ctypes.c_int32),
+        ("new_g", ctypes.c_int32),
+        ("ntap", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "rdx_version": (ctypes.c_char_p, []),
@@ -94,6 +112,10 @@ SIGNATURES = {
                               c_i64, ctypes.POINTER(c_int), c_f32, c_vp, c_vp]),
     "rdx_window_gather": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 4 + [c_int, c_i64, c_vp, c_vp]),
     "rdx_segment_reduce": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rdx_ingest_taps": (c_int, [c_int, c_int, c_int, c_f64, c_vp, c_vp, c_i64] + [ctypes.POINTER(c_int)] * 4),
+    "rdx_ingest_plan": (c_int, [c_int, c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 3),
+    "rdx_ingest_resample": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(IngestJob),
+                                    c_int, c_vp]),
     "rdx_bnselu_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_bnselu_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_res_tail_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

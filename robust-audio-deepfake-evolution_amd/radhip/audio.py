@@ -32,15 +32,18 @@ SIGNATURES = {
                                     ctypes.POINTER(c_int)]),
     "rdx_flac_read_batch": (c_int, [ctypes.POINTER(c_str), c_int, c_vp, ctypes.POINTER(c_i64),
                                     ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_int]),
+    "rdx_flac_read_batch_interleaved": (c_int, [ctypes.POINTER(c_str), c_int, c_vp, ctypes.POINTER(c_i64),
+                                                ctypes.POINTER(c_i64), ctypes.POINTER(c_int), ctypes.POINTER(c_i64),
+                                                ctypes.POINTER(c_int), c_int]),
 }
 
 _lock = threading.Lock()
 _lib = None
 
 
-def header_symbols():
+def header_symbols(header="radio.h"):
     import re
-    text = open(os.path.join(_HERE, "..", "..", "include", "radio.h")).read()
+    text = open(os.path.join(_HERE, "..", "..", "include", header)).read()
     return sorted(set(re.findall(r"^\s*(?:const char\*|int64_t|int)\s+(rdx_\w+)\s*\(", text, re.M)))
 
 
@@ -152,3 +155,72 @@ def read_batch(paths, out=None, threads=8):
         bad = int(np.nonzero(status)[0][0])
         _check(int(status[bad]), str(paths[bad]))
     return out, offsets, lens
+
+
+def _is_wav(path):
+    return str(path).lower().endswith(".wav")
+
+
+def probe_any(path):
+    """(frames, channels, sample_rate) of a .flac (STREAMINFO; frames 0 when the encoder left the count out) or a
+    .wav (its header, through scipy's memory map: no sample is read)."""
+    path = str(path)
+    if _is_wav(path):
+        from scipy.io import wavfile
+        try:
+            sr, x = wavfile.read(path, mmap=True)
+        except (OSError, ValueError) as e:
+            raise AudioReadError(f"{path}: {e}")
+        return int(x.shape[0]), (1 if x.ndim == 1 else int(x.shape[1])), int(sr)
+    frames, ch, sr, _ = probe(path)
+    return frames, ch, sr
+
+
+def read_batch_interleaved(paths, out=None, threads=8):
+    """Decode .flac (native, in parallel) and .wav (scipy, as `read` normalises them) files of any channel count
+    into one float32 buffer, file i as interleaved [frames, channels] at offsets[i]. Returns (buffer, offsets,
+    frames, channels, rates), all per file. `out` as in read_batch."""
+    paths = [str(p) for p in paths]
+    n = len(paths)
+    frames, chans, rates = (np.empty(n, dtype=t) for t in (np.int64, np.int32, np.int64))
+    for i, p in enumerate(paths):
+        frames[i], chans[i], rates[i] = probe_any(p)
+        if frames[i] == 0:
+            raise AudioReadError(f"{p}: no samples (the header gives 0 frames)")
+    sizes = frames * chans
+    offsets = np.zeros(n, dtype=np.int64)
+    if n:
+        offsets[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    if out is None:
+        out = np.empty(total, dtype=np.float32)
+    if hasattr(out, "data_ptr"):
+        if out.numel() < total:
+            raise ValueError("read_batch_interleaved: output buffer too small")
+        ptr, host = out.data_ptr(), out.numpy()
+    else:
+        if out.size < total:
+            raise ValueError("read_batch_interleaved: output buffer too small")
+        ptr, host = out.ctypes.data, out
+    flac = [i for i, p in enumerate(paths) if not _is_wav(p)]
+    if flac:
+        m = len(flac)
+        cpaths = (c_str * m)(*[os.fsencode(paths[i]) for i in flac])
+        offs, caps, ch = (np.ascontiguousarray(a[flac]) for a in (offsets, frames, chans))
+        got = np.zeros(m, dtype=np.int64)
+        status = np.zeros(m, dtype=np.int32)
+        code = lib().rdx_flac_read_batch_interleaved(cpaths, m, ptr, offs.ctypes.data_as(ctypes.POINTER(c_i64)),
+                                                     caps.ctypes.data_as(ctypes.POINTER(c_i64)),
+                                                     ch.ctypes.data_as(ctypes.POINTER(c_int)),
+                                                     got.ctypes.data_as(ctypes.POINTER(c_i64)),
+                                                     status.ctypes.data_as(ctypes.POINTER(c_int)), int(threads))
+        if code != 0:
+            bad = int(np.nonzero(status)[0][0])
+            _check(int(status[bad]), paths[flac[bad]])
+    for i, p in enumerate(paths):
+        if _is_wav(p):
+            x, _ = read(p)
+            if x.shape[0] != frames[i]:
+                raise AudioReadError(f"{p}: {x.shape[0]} frames read, {frames[i]} in the header")
+            host[offsets[i]:offsets[i] + sizes[i]] = x.reshape(-1)     # float64 -> float32, as read().astype(float32)
+    return out, offsets, frames, chans, rates

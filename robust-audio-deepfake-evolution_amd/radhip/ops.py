@@ -896,6 +896,83 @@ def segment_reduce(scores, seg):
     return f[0], f[1], f[2], arg
 
 
+def ingest_taps(orig_freq, new_freq=16000, lowpass_width=6, rolloff=0.99):
+    """The compact taps of the resampling filter (rdx_ingest_taps, host): (first int32 [new_g], taps float32
+    [ntap, new_g] tap-major, width, orig_g, new_g)."""
+    nt, w, og, ng = (ctypes.c_int() for _ in range(4))
+    refs = [ctypes.byref(v) for v in (nt, w, og, ng)]
+    check(lib().rdx_ingest_taps(int(orig_freq), int(new_freq), int(lowpass_width), float(rolloff), None, None, 0,
+                                *refs), "ingest_taps")
+    first = np.empty(ng.value, dtype=np.int32)
+    taps = np.empty((nt.value, ng.value), dtype=np.float32)
+    check(lib().rdx_ingest_taps(int(orig_freq), int(new_freq), int(lowpass_width), float(rolloff), first.ctypes.data,
+                                taps.ctypes.data, taps.size, *refs), "ingest_taps")
+    return first, taps, w.value, og.value, ng.value
+
+
+def ingest_plan(orig_g, new_g, ntap, channels=1):
+    """(outputs per workgroup, LDS bytes, taps staged in LDS) of rdx_ingest_resample for one rate and channel count."""
+    ob, lds, in_lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib().rdx_ingest_plan(int(orig_g), int(new_g), int(ntap), int(channels), ctypes.byref(ob), ctypes.byref(lds),
+                                ctypes.byref(in_lds)), "ingest_plan")
+    return ob.value, lds.value, bool(in_lds.value)
+
+
+def ingest_out_len(frames, orig_freq, new_freq=16000):
+    """ceil(new_freq * frames / orig_freq): the length rdx_ingest_resample writes (torchaudio's rule)."""
+    return -(-int(new_freq) * int(frames) // int(orig_freq))
+
+
+class IngestTables:
+    """The tap tables of every source rate seen so far, packed in two device buffers (first, taps) that
+    rdx_ingest_resample reads. A rate's table is built once, on the host, and uploaded when it is first asked for."""
+
+    def __init__(self, device, new_freq=16000):
+        self.device, self.new_freq = torch.device(device), int(new_freq)
+        self.rates = {}                 # rate -> (first_offset, taps_offset, ntap, width, orig_g, new_g)
+        self._first, self._taps = [], []
+        self.first = self.taps = None
+
+    def entry(self, rate):
+        rate = int(rate)
+        if rate not in self.rates:
+            if rate == self.new_freq:
+                # no filter (as the oracle's resample returns its input): one tap of 1 at the frame itself, so a
+                # multi-channel recording at the target rate is down-mixed only
+                first, taps, width, og, ng = np.ones(1, np.int32), np.ones((1, 1), np.float32), 1, 1, 1
+            else:
+                first, taps, width, og, ng = ingest_taps(rate, self.new_freq)
+            self.rates[rate] = (sum(a.size for a in self._first), sum(a.size for a in self._taps), taps.shape[0],
+                                width, og, ng)
+            self._first.append(first)
+            self._taps.append(taps.reshape(-1))
+            self.first = torch.from_numpy(np.concatenate(self._first)).to(self.device)
+            self.taps = torch.from_numpy(np.concatenate(self._taps)).to(self.device)
+        return self.rates[rate]
+
+    def job(self, rate, channels, frames, in_offset, out_offset):
+        fo, to, ntap, width, og, ng = self.entry(rate)
+        return _lib.IngestJob(int(in_offset), int(frames), int(out_offset), fo, to, int(channels), og, ng, ntap, width,
+                              0)
+
+
+def ingest_resample(in_flat, out_flat, tables, jobs):
+    """Down-mix and resample recordings on the device (rdx_ingest_resample): job j reads interleaved float32
+    [frames, channels] at in_flat[in_offset:] and writes mono float32 [ingest_out_len] at out_flat[out_offset:].
+    jobs: IngestJob records from tables.job(...); any number of them."""
+    _require_gpu(in_flat, out_flat)
+    for t in (in_flat, out_flat):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("ingest_resample: buffers must be contiguous float32 tensors")
+    if not jobs:
+        return out_flat
+    arr = (_lib.IngestJob * len(jobs))(*jobs)
+    check(lib().rdx_ingest_resample(_p(in_flat), in_flat.numel(), _p(out_flat), out_flat.numel(), _p(tables.first),
+                                    tables.first.numel(), _p(tables.taps), tables.taps.numel(), arr, len(jobs),
+                                    _stream(in_flat)), "ingest_resample")
+    return out_flat
+
+
 # -------------------------------------------------------- SincNet residual stack (NHWC) -------
 def _nhwc(t):
     return t.contiguous(memory_format=torch.channels_last)

@@ -14,6 +14,11 @@ The window rule (`window_table`, the only statement of it):
 Data path: recordings are decoded by the native batch reader into one packed pinned buffer (radhip.audio.read_batch),
 uploaded in one copy, cut into model inputs on the device by rdx_window_gather, scored through radhip.infer._scores
 and reduced on the device by rdx_segment_reduce (csrc/recwin.hip). There is no CPU path.
+
+With convert=True a recording may have any integer sample rate and channel count (.flac or .wav): the chunk is
+uploaded as it was decoded, interleaved, and rdx_ingest_resample (csrc/ingest.hip) writes its channel mean, resampled
+to 16 kHz by the filter the training augmentation uses, into the packed buffer the window gather reads. The window
+rule then applies to the converted signal: every length and window start in a record is in 16 kHz samples.
 """
 import numpy as np
 import torch
@@ -21,7 +26,7 @@ import torch
 from . import audio
 from .data import CUT, _PinnedBuf
 from .infer import _scores
-from .ops import segment_reduce, window_gather
+from .ops import IngestTables, ingest_out_len, ingest_resample, segment_reduce, window_gather
 
 SAMPLE_RATE = 16000
 # Packed samples resident per chunk of recordings: 2^24 fp32 samples = 64 MiB on the host (pinned) and on the device,
@@ -74,6 +79,24 @@ def _chunks(lens, cap):
         yield i0, len(lens)
 
 
+def _chunks_convert(raw, lens, cap):
+    """_chunks under two caps: [i0, i1) runs whose raw interleaved floats and whose converted samples both stay
+    within cap (one recording at least)."""
+    i0, a, b = 0, 0, 0
+    for i, (r, n) in enumerate(zip(raw, lens)):
+        if i > i0 and (a + r > cap or b + n > cap):
+            yield i0, i
+            i0, a, b = i, 0, 0
+        a, b = a + int(r), b + int(n)
+    if len(lens) > i0:
+        yield i0, len(lens)
+
+
+def converted_lengths(frames, rates):
+    """The 16 kHz length of every recording: ceil(16000 * frames / rate), what rdx_ingest_resample writes."""
+    return np.array([ingest_out_len(f, r, SAMPLE_RATE) for f, r in zip(frames, rates)], dtype=np.int64)
+
+
 class RecordingScorer:
     """One record per recording: {name, n_samples, n_windows, score, min, max, argmin_start} and, with
     timeline=True, window_starts / window_scores. The score of a window is the bona-fide logit (or the OC-Softmax
@@ -86,10 +109,16 @@ class RecordingScorer:
     list is; a batch may straddle two chunks. What grows with the list is one fp32 score per window and the records.
 
     amp: "x3" (default, the scorer of main.py --eval), "fp32", "bf16" or "fp16", as radhip.infer._scores takes them.
+
+    convert=True: recordings of any integer sample rate and channel count, .flac or .wav, are down-mixed (channel
+    mean) and resampled to 16 kHz on the device first (rdx_ingest_resample). n_samples, window_starts and
+    argmin_start are then in 16 kHz samples, and every record also carries source_rate, source_channels and
+    source_frames. A chunk holds at most CHUNK_SAMPLES floats both as decoded and as converted. A recording that is
+    already mono 16 kHz is copied, not filtered. The tap tables are built once per source rate and stay on the device.
     """
 
     def __init__(self, model, device, criterion=None, amp="x3", batch_size=32, hop=32300, reduce="mean", win=CUT,
-                 threads=8):
+                 threads=8, convert=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("RecordingScorer runs the HIP path and needs a ROCm GPU (there is no CPU path)")
@@ -103,12 +132,17 @@ class RecordingScorer:
         self.model, self.criterion, self.amp = model, criterion, AMP[amp]
         self.B, self.hop, self.win, self.reduce, self.threads = int(batch_size), int(hop), int(win), reduce, threads
         self.pin = _PinnedBuf()
+        self.convert = bool(convert)
+        self.tables = IngestTables(self.device, SAMPLE_RATE) if self.convert else None
 
     # ------------------------------------------------------------------ inputs -----------------
     def score(self, paths, timeline=False):
         """paths: mono 16 kHz .flac files. A file that is not raises AudioReadError naming it before anything is
-        scored (resampling and down-mixing are not done here)."""
+        scored (resampling and down-mixing are not done here). With convert=True: .flac or .wav files of any integer
+        sample rate and channel count; only a file without samples or with a non-positive rate is refused."""
         paths = [str(p) for p in paths]
+        if self.convert:
+            return self._score_converted(paths, timeline)
         lens = np.empty(len(paths), dtype=np.int64)
         for i, p in enumerate(paths):
             frames, ch, sr, _ = audio.probe(p)
@@ -124,30 +158,89 @@ class RecordingScorer:
             audio.read_batch(paths[i0:i1], out=host, threads=self.threads)
         return self._run(paths, lens, load, timeline)
 
-    def score_arrays(self, arrays, names=None, timeline=False):
-        """arrays: 1-D float32 waveforms at 16 kHz."""
+    def _score_converted(self, paths, timeline):
+        n = len(paths)
+        frames, chans, rates = (np.empty(n, dtype=np.int64) for _ in range(3))
+        for i, p in enumerate(paths):
+            frames[i], chans[i], rates[i] = audio.probe_any(p)
+            if frames[i] <= 0:
+                raise audio.AudioReadError(f"{p}: no samples to score (the header gives {frames[i]} frames)")
+            if rates[i] <= 0:
+                raise audio.AudioReadError(f"{p}: sample rate {rates[i]} Hz")
+
+        def load(i0, i1, host):
+            audio.read_batch_interleaved(paths[i0:i1], out=host, threads=self.threads)
+        return self._run(paths, converted_lengths(frames, rates), load, timeline, (frames, chans, rates))
+
+    def score_arrays(self, arrays, names=None, timeline=False, rates=None):
+        """arrays: float32 waveforms, 1-D at 16 kHz. With convert=True an array may also be [n, C] (interleaved
+        channels) and `rates` gives its sample rate: one int for all arrays or one per array (None: 16 kHz); the
+        arrays then take the device path of `score` on files."""
         arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
         names = [f"array {i}" for i in range(len(arrays))] if names is None else [str(n) for n in names]
         if len(names) != len(arrays):
             raise ValueError(f"{len(names)} names for {len(arrays)} arrays")
-        for n, a in zip(names, arrays):
-            if a.ndim != 1:
-                raise ValueError(f"{n}: expected a 1-D waveform, got shape {a.shape}")
+        if not self.convert:
+            if rates is not None:
+                raise ValueError("score_arrays: rates needs a scorer built with convert=True")
+            for n, a in zip(names, arrays):
+                if a.ndim != 1:
+                    raise ValueError(f"{n}: expected a 1-D waveform, got shape {a.shape}")
+        else:
+            for n, a in zip(names, arrays):
+                if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] < 1):
+                    raise ValueError(f"{n}: expected a [n] or [n, channels] waveform, got shape {a.shape}")
         lens = np.array([a.shape[0] for a in arrays], dtype=np.int64)
 
         def load(i0, i1, host):
             o = 0
             for a in arrays[i0:i1]:
-                host[o:o + a.shape[0]] = torch.from_numpy(a)
-                o += a.shape[0]
-        return self._run(names, lens, load, timeline)
+                host[o:o + a.size] = torch.from_numpy(a.reshape(-1))
+                o += a.size
+        if not self.convert:
+            return self._run(names, lens, load, timeline)
+        rates = np.asarray(SAMPLE_RATE if rates is None else rates, dtype=np.int64)
+        if rates.ndim == 0:
+            rates = np.full(len(arrays), int(rates), dtype=np.int64)
+        if rates.shape != (len(arrays),):
+            raise ValueError(f"{rates.size} rates for {len(arrays)} arrays")
+        for n, f, r in zip(names, lens, rates):
+            if f <= 0:
+                raise ValueError(f"{n}: no samples to score (length {int(f)})")
+            if r <= 0:
+                raise ValueError(f"{n}: sample rate {int(r)} Hz")
+        chans = np.array([1 if a.ndim == 1 else a.shape[1] for a in arrays], dtype=np.int64)
+        return self._run(names, converted_lengths(lens, rates), load, timeline, (lens, chans, rates))
 
     # ----------------------------------------------------------------- scoring -----------------
     def _batch_scores(self, xb):
         return _scores(self.model, xb, self.criterion, self.amp).float()
 
+    def _converted(self, i0, i1, lens, load, source):
+        """The packed 16 kHz signal of recordings i0 .. i1 - 1: the chunk is loaded and uploaded as decoded, then
+        down-mixed and resampled on the device. A chunk of mono 16 kHz recordings is its own upload."""
+        frames, chans, rates = (a[i0:i1] for a in source)
+        raw = frames * chans
+        rtotal = int(raw.sum())
+        load(i0, i1, self.pin.get(rtotal))
+        src = self.pin.upload(rtotal, self.device)
+        same = (chans == 1) & (rates == SAMPLE_RATE)
+        if same.all():
+            return src
+        roffs, offs = (np.zeros(i1 - i0, dtype=np.int64) for _ in range(2))
+        np.cumsum(raw[:-1], out=roffs[1:])
+        np.cumsum(lens[i0:i1][:-1], out=offs[1:])
+        sig = torch.empty(int(lens[i0:i1].sum()), device=self.device, dtype=torch.float32)
+        ingest_resample(src, sig, self.tables, [self.tables.job(rates[k], chans[k], frames[k], roffs[k], offs[k])
+                                                for k in np.nonzero(~same)[0]])
+        for k in np.nonzero(same)[0]:
+            sig[offs[k]:offs[k] + frames[k]].copy_(src[roffs[k]:roffs[k] + frames[k]])
+        return sig
+
     @torch.no_grad()
-    def _run(self, names, lens, load, timeline):
+    def _run(self, names, lens, load, timeline, source=None):
+        """source: None, or the (frames, channels, rates) arrays of recordings that `load` delivers interleaved at
+        their own rate; lens are then their 16 kHz lengths."""
         if len(names) == 0:
             return []
         rec, start, seg = window_table(lens, self.hop, self.win, names)
@@ -160,10 +253,15 @@ class RecordingScorer:
             wavlm_x3.drop(self.model)
         try:
             with torch.cuda.device(self.device):
-                for i0, i1 in _chunks(lens, CHUNK_SAMPLES):
-                    total = int(lens[i0:i1].sum())
-                    load(i0, i1, self.pin.get(total))
-                    sig = self.pin.upload(total, self.device)
+                cuts = (_chunks(lens, CHUNK_SAMPLES) if source is None
+                        else _chunks_convert(source[0] * source[1], lens, CHUNK_SAMPLES))
+                for i0, i1 in cuts:
+                    if source is None:
+                        total = int(lens[i0:i1].sum())
+                        load(i0, i1, self.pin.get(total))
+                        sig = self.pin.upload(total, self.device)
+                    else:
+                        sig = self._converted(i0, i1, lens, load, source)
                     clens = lens[i0:i1]
                     offs = np.zeros(i1 - i0, dtype=np.int64)
                     np.cumsum(clens[:-1], out=offs[1:])
@@ -188,6 +286,9 @@ class RecordingScorer:
         pick = {"mean": mean, "min": lo, "max": hi}[self.reduce]
         out = [{"name": names[r], "n_samples": int(lens[r]), "n_windows": int(seg[r + 1] - seg[r]), "score": pick[r],
                 "min": lo[r], "max": hi[r], "argmin_start": int(first[r])} for r in range(len(names))]
+        if source is not None:
+            for r, d in enumerate(out):
+                d["source_frames"], d["source_channels"], d["source_rate"] = (int(a[r]) for a in source)
         if timeline:
             flat = scores.cpu().numpy().astype(np.float32).tolist()
             for r, d in enumerate(out):
