@@ -293,6 +293,44 @@ int rdx_ingest_resample(const float* in, int64_t in_elems, float* out, int64_t o
                         int64_t taps_elems, const rdx_ingest_job* jobs, int njobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Silence trimming for whole-recording scoring (radhip/recordings.py states the rule, trim_plan_np
+ * restates it in numpy; csrc/trim.hip; no reference counterpart). R recordings lie packed in sig as
+ * rdx_window_gather reads them: recording r is lens[r] > 0 fp32 samples at sig + offs[r]. It is cut
+ * into nframes[r] = ceil(lens[r] / RDX_TRIM_FRAME) frames that do not overlap (only the last can be
+ * partial), and frame f of recording r owns element foffs[r] + f of e, scratch and dst. offs, lens,
+ * foffs, nframes and new_offs are HOST arrays of R entries; every other pointer is DEVICE memory. The
+ * caller vouches that the recordings lie inside sig and out, and the frames inside e, scratch and dst,
+ * without overlap. Every argument is checked before the first launch: a null pointer, R <= 0, a
+ * non-positive length or a negative offset is RDX_EINVAL and nothing is written. fp32, no atomics,
+ * fixed reduction orders: two launches give the same bits.
+ * rdx_trim_energy: e[foffs[r] + f] = the mean of x^2 over the samples frame f really has. One wave per
+ *   frame; within 321 * 2^-24 of the exact mean, relatively.
+ * rdx_trim_plan: per recording, peak = max_f e[f]; frame f is active when e[f] > 0 and
+ *   e[f] >= peak * ratio (ratio = 10^(-dB / 10), computed by the caller in double); it is kept when
+ *     RDX_TRIM_GAPS: an active frame lies in [f - pad, f + pad];
+ *     RDX_TRIM_ENDS: first_active - pad <= f <= last_active + pad;
+ *   and a recording without an active frame keeps every frame. dst[foffs[r] + f] = the offset of frame
+ *   f inside the trimmed recording (the summed lengths of the kept frames before it), or -1 when it is
+ *   dropped; kept_len[r] (int64 [R]) = the trimmed length, >= 1. scratch: int32, one per frame. ratio
+ *   outside (0, 1], pad < 0, another mode or nframes[r] != ceil(lens[r] / RDX_TRIM_FRAME) is
+ *   RDX_EINVAL. One workgroup per recording, any number of frames.
+ * rdx_trim_compact: out[new_offs[r] + dst[foffs[r] + f] + i] = sig[offs[r] + f * RDX_TRIM_FRAME + i]
+ *   for every kept frame and every sample i it has: a copy, so out holds the kept frames of every
+ *   recording in order, bit for bit. new_offs[r] >= 0: where the trimmed recording r starts in out
+ *   (a prefix sum of kept_len packs them). out must not overlap sig.
+ * ------------------------------------------------------------------------------------------ */
+#define RDX_TRIM_FRAME 320 /* samples: 20 ms at 16 kHz */
+#define RDX_TRIM_ENDS 0
+#define RDX_TRIM_GAPS 1
+int rdx_trim_energy(const float* sig, const int64_t* offs, const int64_t* lens, const int64_t* foffs,
+                    int R, float* e, void* stream);
+int rdx_trim_plan(const float* e, const int64_t* foffs, const int64_t* nframes, const int64_t* lens,
+                  int R, float ratio, int pad, int mode, int32_t* scratch, int64_t* dst,
+                  int64_t* kept_len, void* stream);
+int rdx_trim_compact(const float* sig, const int64_t* offs, const int64_t* lens, const int64_t* foffs,
+                     const int64_t* dst, const int64_t* new_offs, int R, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * FGM attack, replaces FGM.attack (src/main.py:85-94): for each tensor i,
  *   backup_i = p_i;  if (||g_i|| != 0 && !isnan(||g_i||))  p_i += eps * g_i / ||g_i||
  * Host arrays of ntensors (<= 32) device pointers, fp32. workspace: fp64 [ntensors * 256].

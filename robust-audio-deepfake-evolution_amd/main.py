@@ -15,7 +15,10 @@ Extra flags: --amp {fp16,bf16,fp32} (default fp16: the reference's fp16 autocast
 libradhip_f16.so; bf16 runs the same kernels with bf16 storage, no GradScaler), --eager (no HIP graphs),
 --loader-threads; --score_files LIST [--score_hop N] [--score_reduce {mean,min,max}] [--score_timeline] scores whole
 recordings of any length with --eval_model_weights and writes recording_scores.txt (radhip/recordings.py);
---score_convert lets LIST name .flac / .wav files of any sample rate and channel count (converted on the GPU).
+--score_convert lets LIST name .flac / .wav files of any sample rate and channel count (converted on the GPU);
+--score_trim {ends,gaps} [--score_trim_db DB] [--score_trim_pad FRAMES] drops silent 20 ms frames on the GPU before
+the windows are cut (ends: leading and trailing silence only; gaps: inner pauses too), positions staying those of the
+untrimmed recording.
 
 Differences, all documented in DESIGN.md:
   * data-parallel: one process per GPU (RCCL); the train list is sharded per global micro-step; by default
@@ -309,7 +312,9 @@ class Runner:
         bs = int(self.config.get("test_config", {}).get("batch_size", self.config["batch_size"]))
         scorer = RecordingScorer(model, self.device, criterion=self.criterion, amp=args.eval_amp, batch_size=bs,
                                  hop=args.score_hop, reduce=args.score_reduce, threads=self.threads,
-                                 convert=args.score_convert)
+                                 convert=args.score_convert, trim=args.score_trim,
+                                 trim_db=40.0 if args.score_trim_db is None else args.score_trim_db,
+                                 trim_pad=10 if args.score_trim_pad is None else args.score_trim_pad)
         records = scorer.score(paths, timeline=args.score_timeline)
         write_scores(self.tag / "recording_scores.txt", records)
         if args.score_timeline:
@@ -642,9 +647,26 @@ def parse_args(argv=None):
                         help="with --score_files: accept .flac and .wav recordings of any integer sample rate and "
                              "channel count; they are down-mixed and resampled to 16 kHz on the GPU, and n_samples, "
                              "window starts and argmin_start are in 16 kHz samples")
+    parser.add_argument("--score_trim", default=None, choices=["ends", "gaps"],
+                        help="with --score_files: drop silent 20 ms frames on the GPU before the windows are cut "
+                             "(radhip/recordings.py states the rule). 'ends' drops leading and trailing silence only, "
+                             "'gaps' also the middle of inner pauses; n_samples is then the trimmed length, while "
+                             "window starts and argmin_start stay positions in the untrimmed 16 kHz recording")
+    parser.add_argument("--score_trim_db", type=float, default=None, metavar="DB",
+                        help="a frame is silent when its energy lies more than DB below the recording's loudest "
+                             "frame (> 0, default 40)")
+    parser.add_argument("--score_trim_pad", type=int, default=None, metavar="FRAMES",
+                        help="frames kept on each side of a non-silent frame (>= 0, default 10)")
     args = parser.parse_args(argv)
     if args.score_convert and args.score_files is None:
         parser.error("--score_convert goes with --score_files")
+    for flag in ("score_trim", "score_trim_db", "score_trim_pad"):
+        if getattr(args, flag) is not None and args.score_files is None:
+            parser.error(f"--{flag} goes with --score_files")
+    if args.score_trim_db is not None and not args.score_trim_db > 0:
+        parser.error("--score_trim_db must be positive")
+    if args.score_trim_pad is not None and args.score_trim_pad < 0:
+        parser.error("--score_trim_pad must not be negative")
     if args.score_files is not None:
         if args.eval_model_weights is None:
             parser.error("--score_files requires --eval_model_weights")

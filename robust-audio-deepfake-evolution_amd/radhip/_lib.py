@@ -116,6 +116,11 @@ SIGNATURES = {
     "rdx_ingest_plan": (c_int, [c_int, c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 3),
     "rdx_ingest_resample": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(IngestJob),
                                     c_int, c_vp]),
+    "rdx_trim_energy": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 3 + [c_int, c_vp, c_vp]),
+    "rdx_trim_plan": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 3 + [c_int, c_f32, c_int, c_int, c_vp, c_vp, c_vp,
+                              c_vp]),
+    "rdx_trim_compact": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 3 + [c_vp, ctypes.POINTER(c_i64), c_int, c_vp,
+                                 c_vp]),
     "rdx_bnselu_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_bnselu_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_res_tail_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

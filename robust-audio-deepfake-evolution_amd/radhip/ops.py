@@ -973,6 +973,103 @@ def ingest_resample(in_flat, out_flat, tables, jobs):
     return out_flat
 
 
+# ------------------------------------------------------------------------ silence trimming ----
+TRIM_FRAME = 320                          # RDX_TRIM_FRAME
+TRIM_MODES = {"ends": 0, "gaps": 1}       # RDX_TRIM_ENDS, RDX_TRIM_GAPS
+
+
+def _trim_layout(sig_flat, offs, lens, what):
+    """The checked host tables of packed recordings: (offs, lens, nframes, foffs) as int64 arrays."""
+    _require_gpu(sig_flat)
+    if sig_flat.dtype != torch.float32 or not sig_flat.is_contiguous():
+        raise TypeError(f"{what}: sig must be a contiguous float32 tensor")
+    offs, lens = _i64(offs)[0], _i64(lens)[0]
+    if offs.size != lens.size or lens.size == 0:
+        raise ValueError(f"{what}: offs and lens must pair up, one recording at least")
+    if offs.min() < 0 or lens.min() <= 0 or (offs + lens).max() > sig_flat.numel():
+        raise ValueError(f"{what}: a recording lies outside the {sig_flat.numel()}-sample buffer")
+    nframes = -(-lens // TRIM_FRAME)
+    foffs = np.zeros(lens.size, dtype=np.int64)
+    np.cumsum(nframes[:-1], out=foffs[1:])
+    return offs, lens, nframes, foffs
+
+
+def _ip(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def trim_energy(sig_flat, offs, lens):
+    """float32 [sum of ceil(lens / 320)]: the mean square of every 320-sample frame of the packed recordings, the
+    frames of recording r after those of r - 1 (rdx_trim_energy)."""
+    offs, lens, nframes, foffs = _trim_layout(sig_flat, offs, lens, "trim_energy")
+    e = torch.empty(int(nframes.sum()), device=sig_flat.device, dtype=torch.float32)
+    check(lib().rdx_trim_energy(_p(sig_flat), _ip(offs), _ip(lens), _ip(foffs), lens.size, _p(e), _stream(sig_flat)),
+          "trim_energy")
+    return e
+
+
+def trim_plan(e, lens, mode, db=40.0, pad=10):
+    """int64 [frames + R] on the device, from the frame energies of trim_energy: dst, where each frame starts inside
+    its trimmed recording (-1: dropped), followed by kept_len, the R trimmed lengths (rdx_trim_plan). One buffer, so
+    one copy brings both to the host."""
+    _require_gpu(e)
+    if mode not in TRIM_MODES:
+        raise ValueError(f"trim mode {mode!r} is not one of {sorted(TRIM_MODES)}")
+    if not float(db) > 0 or int(pad) < 0 or int(pad) != pad:
+        raise ValueError(f"trim: need db > 0 and a whole pad >= 0, got db {db}, pad {pad}")
+    lens = _i64(lens)[0]
+    nframes = -(-lens // TRIM_FRAME)
+    foffs = np.zeros(lens.size, dtype=np.int64)
+    np.cumsum(nframes[:-1], out=foffs[1:])
+    total = int(nframes.sum())
+    if e.dtype != torch.float32 or not e.is_contiguous() or e.numel() != total or lens.size == 0 or lens.min() <= 0:
+        raise ValueError(f"trim_plan: e must hold the {total} float32 frame energies of the recordings")
+    plan = torch.empty(total + lens.size, device=e.device, dtype=torch.int64)
+    scratch = torch.empty(total, device=e.device, dtype=torch.int32)
+    ratio = 10.0 ** (-float(db) / 10.0)
+    if np.float32(ratio) <= 0:
+        raise ValueError(f"trim: 10^(-{db} / 10) is zero in float32")
+    check(lib().rdx_trim_plan(_p(e), _ip(foffs), _ip(nframes), _ip(lens), lens.size, ratio, int(pad),
+                              TRIM_MODES[mode], _p(scratch), _p(plan), _p(plan[total:]), _stream(e)), "trim_plan")
+    return plan
+
+
+def trim_compact(sig_flat, offs, lens, dst, new_offs, out):
+    """Copy the kept frames of every recording to out[new_offs[r] + dst ...] (rdx_trim_compact)."""
+    offs, lens, nframes, foffs = _trim_layout(sig_flat, offs, lens, "trim_compact")
+    new_offs = _i64(new_offs)[0]
+    _require_gpu(dst, out)
+    if dst.dtype != torch.int64 or not dst.is_contiguous() or dst.numel() != int(nframes.sum()):
+        raise ValueError("trim_compact: dst must be the int64 plan of these recordings")
+    if out.dtype != torch.float32 or not out.is_contiguous() or new_offs.size != lens.size or new_offs.min() < 0:
+        raise ValueError("trim_compact: out must be a contiguous float32 tensor, new_offs one offset per recording")
+    check(lib().rdx_trim_compact(_p(sig_flat), _ip(offs), _ip(lens), _ip(foffs), _p(dst), _ip(new_offs), lens.size,
+                                 _p(out), _stream(sig_flat)), "trim_compact")
+    return out
+
+
+def trim_silence(sig_flat, offs, lens, mode, db=40.0, pad=10):
+    """Drop the silent frames of packed recordings on the device (the rule: radhip.recordings; csrc/trim.hip).
+    Returns (out, new_lens, kept_ids): the trimmed recordings packed in input order in a float32 device tensor,
+    their lengths (int64 numpy) and, per recording, the source numbers of its kept frames (int64 numpy). The plan
+    (one int64 per frame and one per recording) is the only thing brought to the host, in one copy. When no frame
+    of any recording is dropped and the recordings are already packed, out is sig_flat itself."""
+    offs, lens, nframes, foffs = _trim_layout(sig_flat, offs, lens, "trim_silence")
+    plan = trim_plan(trim_energy(sig_flat, offs, lens), lens, mode, db, pad)
+    host = plan.cpu().numpy()
+    total = int(nframes.sum())
+    new_lens = host[total:].copy()
+    ends = foffs + nframes
+    kept_ids = [np.nonzero(host[a:b] >= 0)[0] for a, b in zip(foffs, ends)]
+    new_offs = np.zeros(lens.size, dtype=np.int64)
+    np.cumsum(new_lens[:-1], out=new_offs[1:])
+    if (new_lens == lens).all() and (new_offs == offs).all():
+        return sig_flat, new_lens, kept_ids
+    out = torch.empty(int(new_lens.sum()), device=sig_flat.device, dtype=torch.float32)
+    trim_compact(sig_flat, offs, lens, plan[:total], new_offs, out)
+    return out, new_lens, kept_ids
+
+
 # -------------------------------------------------------- SincNet residual stack (NHWC) -------
 def _nhwc(t):
     return t.contiguous(memory_format=torch.channels_last)

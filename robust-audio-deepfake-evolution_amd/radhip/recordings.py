@@ -19,6 +19,21 @@ With convert=True a recording may have any integer sample rate and channel count
 uploaded as it was decoded, interleaved, and rdx_ingest_resample (csrc/ingest.hip) writes its channel mean, resampled
 to 16 kHz by the filter the training augmentation uses, into the packed buffer the window gather reads. The window
 rule then applies to the converted signal: every length and window start in a record is in 16 kHz samples.
+
+The trimming rule (trim="ends" or "gaps", off by default; `trim_plan_np` restates it in numpy, csrc/trim.hip runs
+it on the packed chunk between the conversion and the window gather). It applies to one 16 kHz mono signal x of
+length n, the converted one under convert=True, with trim_db > 0 and trim_pad >= 0 frames:
+  * frames: F = 320 samples (20 ms), not overlapping, nf = ceil(n / F); frame f covers [f F, min((f + 1) F, n)), so
+    only the last can be partial; e[f] is the mean of x^2 over the samples the frame really has;
+  * active: peak = max_f e[f]; active[f] = e[f] > 0 and e[f] >= peak 10^(-trim_db / 10). If no frame is active (an
+    all-zero signal) nothing is trimmed;
+  * kept, "gaps": keep[f] iff some active frame lies in [f - trim_pad, f + trim_pad]: an inactive run of at most
+    2 trim_pad frames between active frames stays whole, a longer one loses its middle;
+  * kept, "ends": keep[f] iff first_active - trim_pad <= f <= last_active + trim_pad: inner pauses are never cut;
+  * output: y = the kept frames in order, no cross-fade, m = len(y) >= 1; kept_ids = their source frame numbers;
+  * positions: only the last kept frame can be partial, so sample p of y is source sample
+    src(p) = kept_ids[p // F] F + p % F (`trim_src`);
+  * windows: the window rule then applies to y unchanged, the tiling of a y no longer than a window included.
 """
 import numpy as np
 import torch
@@ -26,7 +41,8 @@ import torch
 from . import audio
 from .data import CUT, _PinnedBuf
 from .infer import _scores
-from .ops import IngestTables, ingest_out_len, ingest_resample, segment_reduce, window_gather
+from .ops import (TRIM_FRAME, TRIM_MODES, IngestTables, ingest_out_len, ingest_resample, segment_reduce, trim_silence,
+                  window_gather)
 
 SAMPLE_RATE = 16000
 # Packed samples resident per chunk of recordings: 2^24 fp32 samples = 64 MiB on the host (pinned) and on the device,
@@ -65,6 +81,57 @@ def window_samples(x, start, win=CUT):
     if n <= win:
         return x[np.arange(win) % n]
     return x[start:start + win]
+
+
+def frame_energy_np(x):
+    """float64 [ceil(n / 320)]: the mean of x^2 over the samples each frame really has (what rdx_trim_energy
+    computes in fp32)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = x.size
+    if n == 0:
+        raise ValueError("frame_energy_np: no samples")
+    nf = -(-n // TRIM_FRAME)
+    sq = np.zeros(nf * TRIM_FRAME, dtype=np.float64)
+    sq[:n] = x * x
+    count = np.minimum(TRIM_FRAME, n - TRIM_FRAME * np.arange(nf, dtype=np.int64))
+    return sq.reshape(nf, TRIM_FRAME).sum(axis=1) / count
+
+
+def trim_plan_np(x, mode, db=40.0, pad=10):
+    """The numpy restatement of the trimming rule, in float64: (keep bool [nf], kept_ids int64, m), m = the length
+    of the trimmed signal (what rdx_trim_plan decides for one recording)."""
+    if mode not in TRIM_MODES:
+        raise ValueError(f"trim mode {mode!r} is not one of {sorted(TRIM_MODES)}")
+    if not db > 0 or pad < 0:
+        raise ValueError(f"trim_plan_np: need db > 0 and pad >= 0, got db {db}, pad {pad}")
+    e = frame_energy_np(x)
+    n, nf, pad = np.asarray(x).size, e.size, int(pad)
+    active = (e > 0) & (e >= e.max() * 10.0 ** (-float(db) / 10.0))
+    f = np.arange(nf, dtype=np.int64)
+    if not active.any():
+        keep = np.ones(nf, dtype=bool)
+    elif mode == "gaps":
+        before = np.concatenate([[0], np.cumsum(active)])       # before[k]: active frames among the first k
+        keep = before[np.minimum(f + pad + 1, nf)] - before[np.maximum(f - pad, 0)] > 0
+    else:
+        on = np.nonzero(active)[0]
+        keep = (f >= on[0] - pad) & (f <= on[-1] + pad)
+    kept_ids = np.nonzero(keep)[0].astype(np.int64)
+    m = int(np.minimum(TRIM_FRAME, n - TRIM_FRAME * kept_ids).sum())
+    return keep, kept_ids, m
+
+
+def trim_apply_np(x, kept_ids):
+    """y: the kept frames of x in order (what rdx_trim_compact writes for one recording)."""
+    x = np.asarray(x).reshape(-1)
+    idx = (TRIM_FRAME * np.asarray(kept_ids, dtype=np.int64)[:, None] + np.arange(TRIM_FRAME)).reshape(-1)
+    return x[idx[idx < x.size]]
+
+
+def trim_src(kept_ids, p):
+    """src(p): the source sample of sample(s) p of the trimmed signal."""
+    p = np.asarray(p, dtype=np.int64)
+    return np.asarray(kept_ids, dtype=np.int64)[p // TRIM_FRAME] * TRIM_FRAME + p % TRIM_FRAME
 
 
 def _chunks(lens, cap):
@@ -115,10 +182,19 @@ class RecordingScorer:
     argmin_start are then in 16 kHz samples, and every record also carries source_rate, source_channels and
     source_frames. A chunk holds at most CHUNK_SAMPLES floats both as decoded and as converted. A recording that is
     already mono 16 kHz is copied, not filtered. The tap tables are built once per source rate and stay on the device.
+
+    trim="ends" or "gaps" (None: off): the silent frames of every recording are dropped on the device first, by the
+    trimming rule in this module's docstring with trim_db (> 0) and trim_pad (frames, >= 0), after the conversion
+    when convert=True. The windows then cover the trimmed signal: n_samples is its length, and every record also
+    carries untrimmed_samples (the 16 kHz length before trimming) and kept_frames. argmin_start and window_starts
+    stay positions in the untrimmed 16 kHz signal, src(start), and with timeline=True window_ends gives
+    src(last sample the window covers) + 1: in "gaps" mode a window can span more than `win` source samples. The
+    window table is built chunk by chunk, from the trimmed lengths that come back from the device (one copy of the
+    plan per chunk).
     """
 
     def __init__(self, model, device, criterion=None, amp="x3", batch_size=32, hop=32300, reduce="mean", win=CUT,
-                 threads=8, convert=False):
+                 threads=8, convert=False, trim=None, trim_db=40.0, trim_pad=10):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("RecordingScorer runs the HIP path and needs a ROCm GPU (there is no CPU path)")
@@ -129,6 +205,13 @@ class RecordingScorer:
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
         window_table([1], hop, win)     # the rule's own check of hop and win
+        if trim is not None and trim not in TRIM_MODES:
+            raise ValueError(f"trim {trim!r} is not one of {sorted(TRIM_MODES)} (or None)")
+        if not float(trim_db) > 0:
+            raise ValueError(f"trim_db must be positive, got {trim_db}")
+        if int(trim_pad) != trim_pad or trim_pad < 0:
+            raise ValueError(f"trim_pad must be a whole number of frames >= 0, got {trim_pad}")
+        self.trim, self.trim_db, self.trim_pad = trim, float(trim_db), int(trim_pad)
         self.model, self.criterion, self.amp = model, criterion, AMP[amp]
         self.B, self.hop, self.win, self.reduce, self.threads = int(batch_size), int(hop), int(win), reduce, threads
         self.pin = _PinnedBuf()
@@ -243,6 +326,8 @@ class RecordingScorer:
         their own rate; lens are then their 16 kHz lengths."""
         if len(names) == 0:
             return []
+        if self.trim is not None:
+            return self._run_trimmed(names, lens, load, timeline, source)
         rec, start, seg = window_table(lens, self.hop, self.win, names)
         self.model.eval()
         xb = torch.empty(self.B, self.win, device=self.device, dtype=torch.float32)
@@ -293,6 +378,79 @@ class RecordingScorer:
             flat = scores.cpu().numpy().astype(np.float32).tolist()
             for r, d in enumerate(out):
                 d["window_starts"] = start[seg[r]:seg[r + 1]].tolist()
+                d["window_scores"] = flat[int(seg[r]):int(seg[r + 1])]
+        return out
+
+    def _run_trimmed(self, names, lens, load, timeline, source):
+        """_run with trimming: a chunk's window table exists only once its trimmed lengths are back from the device,
+        so the table is built chunk by chunk and appended; batches still straddle chunks and only the last is
+        partial. Window positions are turned into source positions while the chunk's kept_ids are at hand."""
+        window_table(lens, self.hop, self.win, names)       # names a recording without samples before any work
+        self.model.eval()
+        xb = torch.empty(self.B, self.win, device=self.device, dtype=torch.float32)
+        fill, parts = 0, []
+        tlens, kept, counts, first, last = [], [], [], [], []   # per recording (2) and per window (3), by chunk
+        if self.amp == "x3":
+            from . import wavlm_x3
+            wavlm_x3.drop(self.model)
+        try:
+            with torch.cuda.device(self.device):
+                cuts = (_chunks(lens, CHUNK_SAMPLES) if source is None
+                        else _chunks_convert(source[0] * source[1], lens, CHUNK_SAMPLES))
+                for i0, i1 in cuts:
+                    if source is None:
+                        total = int(lens[i0:i1].sum())
+                        load(i0, i1, self.pin.get(total))
+                        sig = self.pin.upload(total, self.device)
+                    else:
+                        sig = self._converted(i0, i1, lens, load, source)
+                    offs = np.zeros(i1 - i0, dtype=np.int64)
+                    np.cumsum(lens[i0:i1][:-1], out=offs[1:])
+                    sig, clens, ids = trim_silence(sig, offs, lens[i0:i1], self.trim, self.trim_db, self.trim_pad)
+                    offs = np.zeros(i1 - i0, dtype=np.int64)
+                    np.cumsum(clens[:-1], out=offs[1:])
+                    rec, start, seg = window_table(clens, self.hop, self.win, names[i0:i1])
+                    stop = np.minimum(start + self.win, clens[rec]) - 1     # the last sample of the window's span
+                    tlens.append(clens)
+                    kept.append(np.array([k.size for k in ids], dtype=np.int64))
+                    counts.append(np.diff(seg))
+                    first.append(np.concatenate([trim_src(ids[r], start[seg[r]:seg[r + 1]])
+                                                 for r in range(i1 - i0)]))
+                    last.append(np.concatenate([trim_src(ids[r], stop[seg[r]:seg[r + 1]]) + 1
+                                                for r in range(i1 - i0)]))
+                    w, w1 = 0, int(seg[-1])
+                    while w < w1:
+                        m = min(self.B - fill, w1 - w)
+                        window_gather(sig, offs, clens, rec[w:w + m], start[w:w + m], self.win,
+                                      out=xb[fill:fill + m])
+                        w, fill = w + m, fill + m
+                        if fill == self.B:
+                            parts.append(self._batch_scores(xb))
+                            fill = 0
+                if fill:
+                    parts.append(self._batch_scores(xb[:fill]))
+        finally:
+            if self.amp == "x3":
+                wavlm_x3.drop(self.model)
+        tlens, kept, first, last = (np.concatenate(a) for a in (tlens, kept, first, last))
+        seg = np.zeros(len(names) + 1, dtype=np.int64)
+        np.cumsum(np.concatenate(counts), out=seg[1:])
+        scores = torch.cat(parts)
+        mean, lo, hi, arg = segment_reduce(scores, seg)
+        mean, lo, hi = (t.cpu().numpy().astype(np.float32).tolist() for t in (mean, lo, hi))
+        worst = first[seg[:-1] + arg.cpu().numpy()].tolist()
+        pick = {"mean": mean, "min": lo, "max": hi}[self.reduce]
+        out = [{"name": names[r], "n_samples": int(tlens[r]), "n_windows": int(seg[r + 1] - seg[r]), "score": pick[r],
+                "min": lo[r], "max": hi[r], "argmin_start": int(worst[r]), "untrimmed_samples": int(lens[r]),
+                "kept_frames": int(kept[r])} for r in range(len(names))]
+        if source is not None:
+            for r, d in enumerate(out):
+                d["source_frames"], d["source_channels"], d["source_rate"] = (int(a[r]) for a in source)
+        if timeline:
+            flat = scores.cpu().numpy().astype(np.float32).tolist()
+            for r, d in enumerate(out):
+                d["window_starts"] = first[seg[r]:seg[r + 1]].tolist()
+                d["window_ends"] = last[seg[r]:seg[r + 1]].tolist()
                 d["window_scores"] = flat[int(seg[r]):int(seg[r + 1])]
         return out
 
