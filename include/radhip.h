@@ -331,6 +331,51 @@ int rdx_trim_compact(const float* sig, const int64_t* offs, const int64_t* lens,
                      const int64_t* dst, const int64_t* new_offs, int R, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Locating the spoofed parts of a recording (radhip/recordings.py states the rule, track_np and
+ * segments_np restate it in numpy; csrc/locate.hip; no reference counterpart). The scored signal of
+ * recording r has m[r] > 0 samples and nframes[r] = ceil(m[r] / RDX_TRIM_FRAME) frames, and frame j of
+ * recording r owns element foffs[r] + j of t. m, nwin, foffs and nframes are HOST arrays of R entries;
+ * every other pointer is DEVICE memory. The caller vouches that the frames lie inside t and the slot
+ * arrays without overlap. Every argument is checked before the first launch: a null pointer, R <= 0,
+ * a non-positive length or a negative offset is RDX_EINVAL and nothing is written. Recordings travel
+ * as kernel arguments, 64 per launch. No atomics, fixed operation orders: two launches give the same
+ * bits.
+ * rdx_track_overlap: the per-frame score track. The windows of recording r are those of the window
+ *   rule (one tiled window when m <= win, else starts k * hop for k < n - 1 and m - win for the last)
+ *   and their fp32 scores are scores[seg[r] .. seg[r + 1]) (seg: R + 1 int64 prefix offsets in DEVICE
+ *   memory, as rdx_segment_reduce takes them). nwin[r] is the HOST copy of seg[r + 1] - seg[r]; it must
+ *   equal the rule's count for m[r], hop and win, else RDX_EINVAL (1 <= hop <= win too).
+ *     t[foffs[r] + j] = sum_k ov(k, j) s_k / sum_k ov(k, j),
+ *   ov(k, j) = the samples of frame j's span [j F, min((j + 1) F, m)) inside window k, an integer in
+ *   0 .. F; m <= win: t[.] = s_0. One thread per frame on a flat grid; a thread computes its covering
+ *   windows in closed form (it never searches the window list), sums an fp32 fmaf chain over k
+ *   ascending with the last window last, converts the integer weight sum once and divides once:
+ *   within (c + 3) 2^-24 max|s| of the exact value, c = the covering windows. The cost per frame is
+ *   O(win / hop) windows. A recording set of 2^31 frames or more per launch is RDX_EUNSUPPORTED.
+ * rdx_track_segments: flag[j] = t[j] < thr (strict; a NaN is not flagged); an unflagged run of at most
+ *   `merge` frames with a flagged frame on both sides is bridged; a segment is a maximal run [a, b] of
+ *   flagged or bridged frames with b - a + 1 >= min_frames. Segment number i of recording r (in
+ *   order) is written to slot foffs[r] + i: seg_a / seg_b (int32, frame numbers inside the
+ *   recording); count[r] (int32 [R]) = its segments, at most ceil(nframes[r] / 2), so frame-sized slot
+ *   arrays always suffice. Slots at or past count[r] are not written. One workgroup of 256 threads
+ *   per recording walks the frames in tiles of 1024 once, three scans per tile with carries in LDS; no
+ *   scratch memory. thr NaN, merge < 0 or min_frames < 1 is RDX_EINVAL; nframes[r] > 2^31 - 2048 is
+ *   RDX_EUNSUPPORTED.
+ * rdx_track_segment_stats: per used slot, over t[a .. b] (bridged frames included): mean (the two-sum
+ *   accumulation and butterfly of rdx_segment_reduce: within (frames - 1) 2^-24 max|t| of the exact
+ *   mean), the exact min and seg_argmin = the first frame (inside the recording) that attains it. One
+ *   wave per slot; a slot at or past count[r] returns at once.
+ * ------------------------------------------------------------------------------------------ */
+int rdx_track_overlap(const float* scores, const int64_t* seg, const int64_t* nwin, const int64_t* m,
+                      const int64_t* foffs, int R, int64_t hop, int64_t win, float* t, void* stream);
+int rdx_track_segments(const float* t, const int64_t* foffs, const int64_t* nframes, int R, float thr,
+                       int merge, int min_frames, int32_t* seg_a, int32_t* seg_b, int32_t* count,
+                       void* stream);
+int rdx_track_segment_stats(const float* t, const int64_t* foffs, const int64_t* nframes, int R,
+                            const int32_t* seg_a, const int32_t* seg_b, const int32_t* count,
+                            float* seg_mean, float* seg_min, int32_t* seg_argmin, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * FGM attack, replaces FGM.attack (src/main.py:85-94): for each tensor i,
  *   backup_i = p_i;  if (||g_i|| != 0 && !isnan(||g_i||))  p_i += eps * g_i / ||g_i||
  * Host arrays of ntensors (<= 32) device pointers, fp32. workspace: fp64 [ntensors * 256].

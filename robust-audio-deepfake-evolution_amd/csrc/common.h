@@ -165,6 +165,16 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// An fp32 sum kept as the unevaluated pair hi + lo: the rounding error of every addition (Knuth's two-sum, exact)
+// goes to lo, so hi + lo misses the true sum of n terms by O(n u^2). Shared by the means of csrc/recwin.hip and
+// csrc/locate.hip.
+__device__ __forceinline__ void two_sum(float& hi, float& lo, float v) {
+  const float s = hi + v;
+  const float b = s - hi;
+  lo += (hi - (s - b)) + (v - b);
+  hi = s;
+}
+
 // Counter-hash dropout shared by every fused kernel: element `idx` is kept iff hash(seed, idx) >= p * 2^32,
 // so a backward pass regenerates the forward mask from (seed, salt, idx) alone.
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {

@@ -49,16 +49,9 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
 // ----------------------------------------------------------------------------- segment reduce ----
 // One wave per segment. Lane l folds scores seg[r] + l, + l + 64, ... in index order, then the 64 partial results
 // meet in a fixed butterfly: the bits depend on the segment alone, not on the grid or on which wave ran it.
-// The sum is kept in fp32 as an unevaluated pair hi + lo: every addition's rounding error (Knuth's two-sum, exact)
+// The sum is kept in fp32 as an unevaluated pair hi + lo (two_sum, common.h): every addition's rounding error
 // goes to lo, so hi + lo misses the true sum by O(n u^2) and the mean is rounded once, at the division. A plain
 // fp32 chain could not promise (n - 1) u max|s| at n = 3 (two additions and the division: up to 8/3 u max|s|).
-__device__ __forceinline__ void two_sum(float& hi, float& lo, float v) {
-  const float s = hi + v;
-  const float b = s - hi;
-  lo += (hi - (s - b)) + (v - b);
-  hi = s;
-}
-
 __global__ __launch_bounds__(256) void segment_reduce_kernel(const float* __restrict__ scores,
                                                              const int64_t* __restrict__ seg, int nseg,
                                                              float* __restrict__ out_mean, float* __restrict__ out_min,

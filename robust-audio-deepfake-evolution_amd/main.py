@@ -18,7 +18,9 @@ recordings of any length with --eval_model_weights and writes recording_scores.t
 --score_convert lets LIST name .flac / .wav files of any sample rate and channel count (converted on the GPU);
 --score_trim {ends,gaps} [--score_trim_db DB] [--score_trim_pad FRAMES] drops silent 20 ms frames on the GPU before
 the windows are cut (ends: leading and trailing silence only; gaps: inner pauses too), positions staying those of the
-untrimmed recording.
+untrimmed recording; --score_segments THR [--score_seg_merge FRAMES] [--score_seg_min FRAMES] and --score_track write
+recording_segments.txt (the runs of frames whose score track lies below THR) and recording_track.txt (the per-frame
+score track), both computed on the GPU from the window scores.
 
 Differences, all documented in DESIGN.md:
   * data-parallel: one process per GPU (RCCL); the train list is sharded per global micro-step; by default
@@ -299,7 +301,7 @@ class Runner:
     def run_score_files(self, model):
         """--score_files: whole recordings of any length, windowed and reduced on the GPU (radhip/recordings.py).
         Both files are written after every recording has been scored, so a bad file leaves nothing partial."""
-        from radhip.recordings import RecordingScorer, write_scores, write_timeline
+        from radhip.recordings import RecordingScorer, write_scores, write_segments, write_timeline, write_track
         args = self.args
         if self.world > 1:
             raise RuntimeError("--score_files scores on one GPU: run it without torch.distributed.run")
@@ -314,11 +316,18 @@ class Runner:
                                  hop=args.score_hop, reduce=args.score_reduce, threads=self.threads,
                                  convert=args.score_convert, trim=args.score_trim,
                                  trim_db=40.0 if args.score_trim_db is None else args.score_trim_db,
-                                 trim_pad=10 if args.score_trim_pad is None else args.score_trim_pad)
+                                 trim_pad=10 if args.score_trim_pad is None else args.score_trim_pad,
+                                 track=args.score_track, segments=args.score_segments,
+                                 seg_merge=10 if args.score_seg_merge is None else args.score_seg_merge,
+                                 seg_min=25 if args.score_seg_min is None else args.score_seg_min)
         records = scorer.score(paths, timeline=args.score_timeline)
         write_scores(self.tag / "recording_scores.txt", records)
         if args.score_timeline:
             write_timeline(self.tag / "recording_timeline.txt", records)
+        if args.score_segments is not None:
+            write_segments(self.tag / "recording_segments.txt", records)
+        if args.score_track:
+            write_track(self.tag / "recording_track.txt", records)
         self.log("Scores saved to {}".format(self.tag / "recording_scores.txt"))
 
     # ------------------------------------------------------------------ train ------------------
@@ -657,9 +666,33 @@ def parse_args(argv=None):
                              "frame (> 0, default 40)")
     parser.add_argument("--score_trim_pad", type=int, default=None, metavar="FRAMES",
                         help="frames kept on each side of a non-silent frame (>= 0, default 10)")
+    parser.add_argument("--score_segments", type=float, default=None, metavar="THR",
+                        help="with --score_files: also write recording_segments.txt, one 'path start end frames mean "
+                             "min' line per run of 20 ms frames whose score track lies below THR (positions in samples "
+                             "of the untrimmed 16 kHz recording; radhip/recordings.py states the rule). The track is "
+                             "the window scores spread over the frames they cover, so localising wants a small "
+                             "--score_hop (3200, say)")
+    parser.add_argument("--score_seg_merge", type=int, default=None, metavar="FRAMES",
+                        help="bridge gaps of at most FRAMES unflagged frames between flagged ones (>= 0, default 10)")
+    parser.add_argument("--score_seg_min", type=int, default=None, metavar="FRAMES",
+                        help="drop segments shorter than FRAMES frames (>= 1, default 25)")
+    parser.add_argument("--score_track", action="store_true",
+                        help="with --score_files: also write recording_track.txt, one 'path frame_start score' line "
+                             "per 20 ms frame of the scored signal")
     args = parser.parse_args(argv)
     if args.score_convert and args.score_files is None:
         parser.error("--score_convert goes with --score_files")
+    for flag in ("score_segments", "score_seg_merge", "score_seg_min"):
+        if getattr(args, flag) is not None and args.score_files is None:
+            parser.error(f"--{flag} goes with --score_files")
+    if args.score_track and args.score_files is None:
+        parser.error("--score_track goes with --score_files")
+    if args.score_segments is not None and not abs(args.score_segments) < float("inf"):
+        parser.error("--score_segments must be finite")
+    if args.score_seg_merge is not None and args.score_seg_merge < 0:
+        parser.error("--score_seg_merge must not be negative")
+    if args.score_seg_min is not None and args.score_seg_min < 1:
+        parser.error("--score_seg_min must be at least 1")
     for flag in ("score_trim", "score_trim_db", "score_trim_pad"):
         if getattr(args, flag) is not None and args.score_files is None:
             parser.error(f"--{flag} goes with --score_files")

@@ -121,7 +121,11 @@ SIGNATURES = {
                               c_vp]),
     "rdx_trim_compact": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 3 + [c_vp, ctypes.POINTER(c_i64), c_int, c_vp,
                                  c_vp]),
-    "rdx_bnselu_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
+    "rdx_track_overlap": (c_int, [c_vp, c_vp] + [ctypes.POINTER(c_i64)] * 3 + [c_int, c_i64, c_i64, c_vp, c_vp]),
+    "rdx_track_segments": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 2 + [c_int, c_f32, c_int, c_int, c_vp, c_vp,
+                                   c_vp, c_vp]),
+    "rdx_track_segment_stats": (c_int, [c_vp] + [ctypes.POINTER(c_i64)] * 2 + [c_int] + [c_vp] * 7),
+    "rdx_bnselu_fwd":(c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_bnselu_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "rdx_res_tail_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "rdx_res_tail_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),

@@ -1070,6 +1070,82 @@ def trim_silence(sig_flat, offs, lens, mode, db=40.0, pad=10):
     return out, new_lens, kept_ids
 
 
+# ------------------------------------------------------- locating the spoofed parts ----
+def score_track(scores, seg, lens, hop, win):
+    """float32 [sum of ceil(lens / 320)] on the device: the per-frame score track of every recording, the frames of
+    recording r after those of r - 1 (rdx_track_overlap; the rule: radhip.recordings, track_np). scores: the fp32
+    window scores on the device; seg: host integer prefix offsets of the recordings' windows, as segment_reduce takes
+    them; lens: the lengths of the scored signals. Every recording must own the windows the window rule gives its
+    length."""
+    _require_gpu(scores)
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise TypeError("score_track: scores must be a contiguous float32 tensor")
+    seg, lens = _i64(seg)[0], _i64(lens)[0]
+    hop, win = int(hop), int(win)
+    if win < 1 or not 1 <= hop <= win:
+        raise ValueError(f"score_track: need 1 <= hop <= win, got hop {hop}, win {win}")
+    if lens.size == 0 or seg.size != lens.size + 1 or lens.min() <= 0:
+        raise ValueError("score_track: one positive length per recording and one more prefix offset than recordings")
+    if seg[0] < 0 or seg[-1] > scores.numel():
+        raise ValueError(f"score_track: seg reaches outside the {scores.numel()} scores")
+    nwin = np.ascontiguousarray(np.diff(seg))
+    want = np.where(lens <= win, 1, 1 - (-(lens - win) // hop))
+    bad = np.nonzero(nwin != want)[0]
+    if bad.size:
+        r = int(bad[0])
+        raise ValueError(f"score_track: recording {r} of {int(lens[r])} samples owns {int(nwin[r])} windows, the "
+                         f"window rule gives {int(want[r])} at hop {hop}")
+    nframes = -(-lens // TRIM_FRAME)
+    foffs = np.zeros(lens.size, dtype=np.int64)
+    np.cumsum(nframes[:-1], out=foffs[1:])
+    seg_dev = torch.from_numpy(seg).to(scores.device)
+    t = torch.empty(int(nframes.sum()), device=scores.device, dtype=torch.float32)
+    check(lib().rdx_track_overlap(_p(scores), _p(seg_dev), _ip(nwin), _ip(lens), _ip(foffs), lens.size, hop, win,
+                                  _p(t), _stream(scores)), "track_overlap")
+    return t
+
+
+def track_segments(t, nframes, thr, merge=10, min_frames=25):
+    """The flagged segments of packed per-frame tracks (rdx_track_segments, rdx_track_segment_stats; the rule:
+    radhip.recordings, segments_np). t: any float32 device tensor that holds the nframes[r] frames of recording r
+    after those of r - 1. Returns one (a, b, mean, min, argmin) per recording, host arrays with one entry per
+    segment: first and last frame (int64), the fp32 mean and minimum of t[a .. b] and the first frame that attains
+    the minimum (int64). Counts, bounds and statistics come back in one copy."""
+    _require_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError("track_segments: t must be a contiguous float32 tensor")
+    nframes = _i64(nframes)[0]
+    total = int(nframes.sum())
+    if nframes.size == 0 or nframes.min() <= 0 or total != t.numel():
+        raise ValueError(f"track_segments: nframes must be positive and add up to the {t.numel()} frames of t")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(thr)):
+            raise ValueError(f"track_segments: the threshold must be finite in float32, got {thr}")
+    if int(merge) != merge or merge < 0 or int(min_frames) != min_frames or min_frames < 1:
+        raise ValueError(f"track_segments: need whole merge >= 0 and min_frames >= 1, got {merge}, {min_frames}")
+    merge, min_frames = (min(int(v), 2 ** 31 - 1) for v in (merge, min_frames))
+    R = nframes.size
+    foffs = np.zeros(R, dtype=np.int64)
+    np.cumsum(nframes[:-1], out=foffs[1:])
+    # one buffer of 32-bit words: count [R], then a, b, argmin (int32) and mean, min (fp32), one slot per frame each
+    buf = torch.empty(R + 5 * total, device=t.device, dtype=torch.int32)
+    count, a, b, arg = buf[:R], buf[R:R + total], buf[R + total:R + 2 * total], buf[R + 2 * total:R + 3 * total]
+    mean, lo = (buf[R + k * total:R + (k + 1) * total].view(torch.float32) for k in (3, 4))
+    check(lib().rdx_track_segments(_p(t), _ip(foffs), _ip(nframes), R, float(thr), merge, min_frames, _p(a), _p(b),
+                                   _p(count), _stream(t)), "track_segments")
+    check(lib().rdx_track_segment_stats(_p(t), _ip(foffs), _ip(nframes), R, _p(a), _p(b), _p(count), _p(mean), _p(lo),
+                                        _p(arg), _stream(t)), "track_segment_stats")
+    host = buf.cpu().numpy()
+    ints = [host[R + k * total:R + (k + 1) * total] for k in range(3)]
+    floats = [host[R + k * total:R + (k + 1) * total].view(np.float32) for k in (3, 4)]
+    out = []
+    for r in range(R):
+        sl = slice(int(foffs[r]), int(foffs[r]) + int(host[r]))
+        out.append((ints[0][sl].astype(np.int64), ints[1][sl].astype(np.int64), floats[0][sl].copy(),
+                    floats[1][sl].copy(), ints[2][sl].astype(np.int64)))
+    return out
+
+
 # -------------------------------------------------------- SincNet residual stack (NHWC) -------
 def _nhwc(t):
     return t.contiguous(memory_format=torch.channels_last)

@@ -34,6 +34,29 @@ length n, the converted one under convert=True, with trim_db > 0 and trim_pad >=
   * positions: only the last kept frame can be partial, so sample p of y is source sample
     src(p) = kept_ids[p // F] F + p % F (`trim_src`);
   * windows: the window rule then applies to y unchanged, the tiling of a y no longer than a window included.
+
+The locating rule (track=True, segments=thr; off by default; `track_np` and `segments_np` restate it in float64 numpy,
+csrc/locate.hip runs it on the window scores of the whole list). y is the scored signal of one recording, of length
+m: the trimmed signal when trimming is on, otherwise the 16 kHz signal. Its windows are those of the window rule,
+starts a_k and fp32 scores s_k for k < n. F = 320 as above; the frames of y are nfy = ceil(m / F), frame j spans
+[j F, min((j + 1) F, m)), so only the last can be partial.
+  * track: m <= win (one tiled window): t[j] = s_0 for every j. m > win: ov(k, j) = the samples of frame j's span
+    inside [a_k, a_k + win), an integer in 0 .. 320, and t[j] = sum_k ov(k, j) s_k / sum_k ov(k, j), summed over k
+    ascending. Every sample lies in a window, so the denominator is at least the frame's own length. The weights are
+    the plain overlap counts, there is no taper. (m = 64 601, two windows at 0 and 1, 202 frames:
+    t[0] = (320 s_0 + 319 s_1) / 639 and t[201] = (280 s_0 + 281 s_1) / 561, frame 201 spanning [64 320, 64 601).)
+  * segments, on the fp32 track with an fp32 thr, merge >= 0 and min_frames >= 1: flag[j] = t[j] < thr, strictly
+    (scores are bona-fide logits or cosines: lower is more spoof-like); closed[j] = flag[j], or j lies in an unflagged
+    run of at most `merge` frames that has a flagged frame immediately on both sides (a run that touches either end
+    of the recording is never closed); a segment is a maximal run [a, b] of closed frames with
+    b - a + 1 >= min_frames. Per segment: frames = b - a + 1, the mean of t[a .. b] (bridged frames included), the
+    min, and argmin = the first frame that attains it;
+  * positions are reported in the untrimmed 16 kHz signal of length N: track frame j is source frame j without
+    trimming and source frame kept_ids[j] with it (exact, because only the last kept frame can be partial:
+    `track_src_frames`). A segment has start = srcframe(a) F and end = min((srcframe(b) + 1) F, N). In "gaps" mode a
+    segment may span dropped silence, as window_ends may: it is not split, and `frames` says how many were scored.
+The model is trained on whole utterances, so the track is nothing finer than the 4 s window scores spread over the
+frames they cover: its resolution is set by hop and win, not by the 20 ms frame.
 """
 import numpy as np
 import torch
@@ -41,8 +64,8 @@ import torch
 from . import audio
 from .data import CUT, _PinnedBuf
 from .infer import _scores
-from .ops import (TRIM_FRAME, TRIM_MODES, IngestTables, ingest_out_len, ingest_resample, segment_reduce, trim_silence,
-                  window_gather)
+from .ops import (TRIM_FRAME, TRIM_MODES, IngestTables, ingest_out_len, ingest_resample, score_track, segment_reduce,
+                  track_segments, trim_silence, window_gather)
 
 SAMPLE_RATE = 16000
 # Packed samples resident per chunk of recordings: 2^24 fp32 samples = 64 MiB on the host (pinned) and on the device,
@@ -134,6 +157,80 @@ def trim_src(kept_ids, p):
     return np.asarray(kept_ids, dtype=np.int64)[p // TRIM_FRAME] * TRIM_FRAME + p % TRIM_FRAME
 
 
+def track_src_frames(kept_ids, n, m):
+    """kept_ids, as the source frame of every frame of the trimmed signal of length m cut from a signal of length n.
+    Frame j of the trimmed signal is exactly source frame kept_ids[j], because a kept frame other than the last is
+    whole: only the source's last frame can be partial, and it can only be kept last. Asserted here."""
+    ids = np.asarray(kept_ids, dtype=np.int64)
+    assert ids.size >= 1 and (np.diff(ids) > 0).all() and ((ids[:-1] + 1) * TRIM_FRAME <= n).all(), \
+        "a kept frame before the last is partial"
+    assert m == (ids.size - 1) * TRIM_FRAME + min(TRIM_FRAME, n - int(ids[-1]) * TRIM_FRAME), (m, n, ids.size)
+    return ids
+
+
+def track_np(m, scores, hop, win=CUT):
+    """The numpy restatement of the track rule, in float64: t [ceil(m / 320)] of one scored signal of length m whose
+    windows (window_table([m], hop, win)) have `scores` (what rdx_track_overlap computes in fp32)."""
+    m = int(m)
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    _, start, _ = window_table([m], hop, win)
+    if s.size != start.size:
+        raise ValueError(f"track_np: {s.size} scores for the {start.size} windows of {m} samples at hop {hop}")
+    nfy = -(-m // TRIM_FRAME)
+    if m <= win:
+        return np.full(nfy, s[0])
+    num, den = np.zeros(nfy, dtype=np.float64), np.zeros(nfy, dtype=np.int64)
+    for a, sk in zip(start.tolist(), s.tolist()):       # k ascending
+        j = np.arange(a // TRIM_FRAME, (a + win - 1) // TRIM_FRAME + 1, dtype=np.int64)
+        ov = np.minimum(np.minimum((j + 1) * TRIM_FRAME, m), a + win) - np.maximum(j * TRIM_FRAME, a)
+        num[j] += ov * sk
+        den[j] += ov
+    return num / den
+
+
+def segments_np(t, thr, merge=10, min_frames=25):
+    """The numpy restatement of the segment rule on one fp32 track: (a, b, mean, min, argmin), one entry per segment:
+    first and last frame (int64), the float64 mean and the fp32 minimum of t[a .. b] and the first frame that attains
+    it (what rdx_track_segments and rdx_track_segment_stats compute for one recording)."""
+    t = np.asarray(t, dtype=np.float32).reshape(-1)
+    with np.errstate(over="ignore"):
+        thr32 = np.float32(thr)
+    if t.size == 0 or not np.isfinite(thr32):
+        raise ValueError(f"segments_np: need a track of one frame at least and a finite threshold, got {thr}")
+    if int(merge) != merge or merge < 0 or int(min_frames) != min_frames or min_frames < 1:
+        raise ValueError(f"segments_np: need whole merge >= 0 and min_frames >= 1, got {merge}, {min_frames}")
+    nf = t.size
+
+    def runs(mask):     # [first, last + 1) of every maximal run of True
+        d = np.diff(np.concatenate([[0], mask.astype(np.int8), [0]]))
+        return np.nonzero(d == 1)[0], np.nonzero(d == -1)[0]
+    flag = t < thr32
+    u0, u1 = runs(~flag)
+    ok = (u0 > 0) & (u1 < nf) & (u1 - u0 <= merge)
+    delta = np.zeros(nf + 1, dtype=np.int64)
+    delta[u0[ok]] += 1
+    delta[u1[ok]] -= 1
+    closed = flag | (np.cumsum(delta[:-1]) > 0)
+    a, e = runs(closed)
+    keep = e - a >= min_frames
+    a, b = a[keep].astype(np.int64), e[keep].astype(np.int64) - 1
+    mean = np.array([t[x:y + 1].astype(np.float64).mean() for x, y in zip(a, b)], dtype=np.float64)
+    lo = np.array([t[x:y + 1].min() for x, y in zip(a, b)], dtype=np.float32)
+    arg = np.array([x + int(np.argmin(t[x:y + 1])) for x, y in zip(a, b)], dtype=np.int64)
+    return a, b, mean, lo, arg
+
+
+def segment_span(a, b, n_source, kept_ids=None):
+    """(start, end) of segments [a, b] (track frames) as sample positions in the untrimmed signal of n_source
+    samples: start = srcframe(a) F, end = min((srcframe(b) + 1) F, n_source), srcframe(j) = j, or kept_ids[j] under
+    trimming."""
+    a, b = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
+    if kept_ids is not None:
+        ids = np.asarray(kept_ids, dtype=np.int64)
+        a, b = ids[a], ids[b]
+    return a * TRIM_FRAME, np.minimum((b + 1) * TRIM_FRAME, int(n_source))
+
+
 def _chunks(lens, cap):
     """[i0, i1) runs of recordings whose packed samples stay within cap (one recording at least)."""
     i0, total = 0, 0
@@ -191,10 +288,24 @@ class RecordingScorer:
     src(last sample the window covers) + 1: in "gaps" mode a window can span more than `win` source samples. The
     window table is built chunk by chunk, from the trimmed lengths that come back from the device (one copy of the
     plan per chunk).
+
+    track=True and segments=thr (a float; None: off) locate the spoofed parts by the locating rule in this module's
+    docstring, on the device, once the window scores of the whole list exist. track=True adds track_scores, one fp32
+    value per 20 ms frame of the scored signal, and under trimming track_frames, the source frame number of each.
+    segments=thr adds segments, a list of {start, end, frames, mean, min, argmin_start} with positions in samples
+    of the untrimmed 16 kHz signal, for the runs of frames whose track lies below thr after gaps of at most
+    seg_merge frames are bridged and runs shorter than seg_min frames are dropped (defaults: 0.2 s and 0.5 s), and
+    flagged_samples, the samples of the scored signal inside segments (flagged_samples / n_samples is the flagged
+    share). The track is the window scores spread over the frames they cover: its resolution is that of hop and
+    win, so localising wants a small hop (3 200, say, where about 20 windows cover an instant against 2 at the
+    default 32 300, and the forward runs about 10 times as many windows). The track costs 4 bytes per 20 ms on the
+    device for the whole list; with either option on, trimming keeps every recording's kept_ids on the host past its
+    chunk, 8 bytes per kept frame. The segment slots (counts, bounds and statistics) come back in one copy.
     """
 
     def __init__(self, model, device, criterion=None, amp="x3", batch_size=32, hop=32300, reduce="mean", win=CUT,
-                 threads=8, convert=False, trim=None, trim_db=40.0, trim_pad=10):
+                 threads=8, convert=False, trim=None, trim_db=40.0, trim_pad=10, track=False, segments=None,
+                 seg_merge=10, seg_min=25):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("RecordingScorer runs the HIP path and needs a ROCm GPU (there is no CPU path)")
@@ -212,6 +323,16 @@ class RecordingScorer:
         if int(trim_pad) != trim_pad or trim_pad < 0:
             raise ValueError(f"trim_pad must be a whole number of frames >= 0, got {trim_pad}")
         self.trim, self.trim_db, self.trim_pad = trim, float(trim_db), int(trim_pad)
+        if segments is not None:
+            with np.errstate(over="ignore"):
+                if not np.isfinite(np.float32(segments)):
+                    raise ValueError(f"segments (the threshold) must be finite in float32, got {segments}")
+        if int(seg_merge) != seg_merge or seg_merge < 0:
+            raise ValueError(f"seg_merge must be a whole number of frames >= 0, got {seg_merge}")
+        if int(seg_min) != seg_min or seg_min < 1:
+            raise ValueError(f"seg_min must be a whole number of frames >= 1, got {seg_min}")
+        self.track, self.segments = bool(track), None if segments is None else float(segments)
+        self.seg_merge, self.seg_min = int(seg_merge), int(seg_min)
         self.model, self.criterion, self.amp = model, criterion, AMP[amp]
         self.B, self.hop, self.win, self.reduce, self.threads = int(batch_size), int(hop), int(win), reduce, threads
         self.pin = _PinnedBuf()
@@ -379,7 +500,37 @@ class RecordingScorer:
             for r, d in enumerate(out):
                 d["window_starts"] = start[seg[r]:seg[r + 1]].tolist()
                 d["window_scores"] = flat[int(seg[r]):int(seg[r + 1])]
+        if self.track or self.segments is not None:
+            self._locate(out, scores, seg, lens, lens, None)
         return out
+
+    def _locate(self, out, scores, seg, mlens, nsrc, ids):
+        """Adds the track and segment keys to the records `out` of the whole list (the locating rule): scores and seg
+        are the window scores on the device and their per-recording prefix, mlens the lengths of the scored signals,
+        nsrc those of the untrimmed ones, ids the kept_ids of every recording under trimming (else None)."""
+        mlens = np.asarray(mlens, dtype=np.int64)
+        nfr = -(-mlens // TRIM_FRAME)
+        fo = np.zeros(nfr.size + 1, dtype=np.int64)
+        np.cumsum(nfr, out=fo[1:])
+        t = score_track(scores, seg, mlens, self.hop, self.win)
+        if ids is not None:
+            ids = [track_src_frames(k, nsrc[r], mlens[r]) for r, k in enumerate(ids)]
+        if self.track:
+            flat = t.cpu().numpy().tolist()
+            for r, d in enumerate(out):
+                d["track_scores"] = flat[int(fo[r]):int(fo[r + 1])]
+                if ids is not None:
+                    d["track_frames"] = ids[r].tolist()
+        if self.segments is not None:
+            found = track_segments(t, nfr, self.segments, self.seg_merge, self.seg_min)
+            for r, (d, (a, b, mean, lo, arg)) in enumerate(zip(out, found)):
+                kept = None if ids is None else ids[r]
+                first, last = segment_span(a, b, nsrc[r], kept)
+                worst, _ = segment_span(arg, arg, nsrc[r], kept)
+                d["segments"] = [{"start": s, "end": e, "frames": n, "mean": mu, "min": v, "argmin_start": w}
+                                 for s, e, n, mu, v, w in zip(first.tolist(), last.tolist(), (b - a + 1).tolist(),
+                                                              mean.tolist(), lo.tolist(), worst.tolist())]
+                d["flagged_samples"] = int((np.minimum((b + 1) * TRIM_FRAME, mlens[r]) - a * TRIM_FRAME).sum())
 
     def _run_trimmed(self, names, lens, load, timeline, source):
         """_run with trimming: a chunk's window table exists only once its trimmed lengths are back from the device,
@@ -390,6 +541,8 @@ class RecordingScorer:
         xb = torch.empty(self.B, self.win, device=self.device, dtype=torch.float32)
         fill, parts = 0, []
         tlens, kept, counts, first, last = [], [], [], [], []   # per recording (2) and per window (3), by chunk
+        locate = self.track or self.segments is not None
+        all_ids = []            # with locate: every recording's kept_ids, kept past its chunk
         if self.amp == "x3":
             from . import wavlm_x3
             wavlm_x3.drop(self.model)
@@ -414,6 +567,8 @@ class RecordingScorer:
                     tlens.append(clens)
                     kept.append(np.array([k.size for k in ids], dtype=np.int64))
                     counts.append(np.diff(seg))
+                    if locate:
+                        all_ids.extend(ids)
                     first.append(np.concatenate([trim_src(ids[r], start[seg[r]:seg[r + 1]])
                                                  for r in range(i1 - i0)]))
                     last.append(np.concatenate([trim_src(ids[r], stop[seg[r]:seg[r + 1]]) + 1
@@ -452,6 +607,8 @@ class RecordingScorer:
                 d["window_starts"] = first[seg[r]:seg[r + 1]].tolist()
                 d["window_ends"] = last[seg[r]:seg[r + 1]].tolist()
                 d["window_scores"] = flat[int(seg[r]):int(seg[r + 1])]
+        if locate:
+            self._locate(out, scores, seg, tlens, lens, all_ids)
         return out
 
 
@@ -470,3 +627,23 @@ def write_timeline(path, records):
         for d in records:
             for st, sco in zip(d["window_starts"], d["window_scores"]):
                 fh.write("{} {} {}\n".format(d["name"], st, sco))
+
+
+def write_segments(path, records):
+    """One line per flagged segment (segments=thr): "name start end frames mean min", positions in samples of the
+    untrimmed 16 kHz signal, floats as write_scores writes them."""
+    with open(path, "w") as fh:
+        for d in records:
+            for s in d["segments"]:
+                fh.write("{} {} {} {} {} {}\n".format(d["name"], s["start"], s["end"], s["frames"], s["mean"],
+                                                      s["min"]))
+
+
+def write_track(path, records):
+    """One line per scored frame (track=True): "name frame_start score", frame_start the frame's first sample in the
+    untrimmed 16 kHz signal."""
+    with open(path, "w") as fh:
+        for d in records:
+            frames = d.get("track_frames", range(len(d["track_scores"])))
+            for f, sco in zip(frames, d["track_scores"]):
+                fh.write("{} {} {}\n".format(d["name"], f * TRIM_FRAME, sco))
